@@ -17,6 +17,12 @@ SEA-4 (in-memory, random-init weights; there is no network access).
 Contract (driver): prints ONE JSON line from rank 0; the timed region is
 bracketed by dist barrier + torch.cuda.synchronize on both sides; the
 reported time is the MAX over ranks.
+
+A plain run does only that: set up, warm up, time --steps rounds, print.
+--dump-outputs DIR additionally writes the last timed round's results as
+DIR/<name>.npy (see dump_outputs) so two builds can be compared output for
+output; --full is where secondary measurements that need runs of their own
+go (there are none yet).
 """
 
 import argparse
@@ -69,12 +75,42 @@ def one_round(job: FLJob, r: int, client_idx) -> None:
     job.algo.test(job, r)
 
 
+def dump_outputs(job: FLJob, out_dir: str) -> None:
+    """Write what the last timed round left behind as <out_dir>/<name>.npy:
+    the aggregated model bank, this rank's locally trained replicas and the
+    round's prequential metrics. Dataset, init weights and batch picks are
+    all seeded, so equal arguments give equal inputs on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    last = {}
+    for rec in job.logger.records[-2:]:
+        last.update(rec)
+    arrays = {
+        "global_params": job.global_params.float().cpu().numpy(),    # [K, P]
+        "replicas": job.replicas.float().cpu().numpy(),         # [nW * K, P]
+        "round_metrics": np.array(
+            [last[k] for k in ("Train/Acc", "Train/Loss",
+                               "Test/Acc", "Test/Loss")], dtype=np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=ROUNDS_DEFAULT)
     p.add_argument("--warmup", type=int, default=WARMUP_DEFAULT)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last round's "
+                        "outputs to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that the "
+                        "headline figure does not need (none exist yet: "
+                        "every figure in the result line comes from the "
+                        "timed rounds themselves)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
 
     comm = Communicator()
     world = comm.world_size
@@ -124,6 +160,9 @@ def main() -> None:
     rounds_per_sec = a.steps / elapsed
     ms_per_step = elapsed / a.steps * 1e3
 
+    if comm.is_root and a.dump_outputs:
+        dump_outputs(job, a.dump_outputs)
+
     if comm.is_root:
         acc = logger.mean("Test/Acc")
         print(json.dumps({
@@ -133,6 +172,7 @@ def main() -> None:
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",

@@ -39,10 +39,11 @@ def test_prepare_and_main_fedavg(tmp_path):
     assert os.path.exists(str(tmp_path / "model_params.pt"))
 
 
-def test_bench_contract():
+def test_bench_contract(tmp_path):
+    dump = str(tmp_path / "dump")
     r = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3",
-         "--warmup", "1"],
+         "--warmup", "1", "--dump-outputs", dump],
         capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-1500:]
     line = [l for l in r.stdout.strip().splitlines()
@@ -60,6 +61,19 @@ def test_bench_contract():
     assert out["scaling"] == "weak"
     assert out["dtype"] == "fp32"
     assert out["higher_is_better"] is True
+    assert out["full"] is False
+    assert out["ms_per_step"] > 0
+    # --dump-outputs: the last timed round's results, one .npy per array
+    gp = np.load(os.path.join(dump, "global_params.npy"))
+    reps = np.load(os.path.join(dump, "replicas.npy"))
+    met = np.load(os.path.join(dump, "round_metrics.npy"))
+    assert gp.dtype == np.float32 and reps.dtype == np.float32
+    assert gp.shape[0] == out["config"]["ensemble_models"]
+    assert reps.shape == (out["config"]["clients_total"] * gp.shape[0],
+                          gp.shape[1])
+    assert met.dtype == np.float64 and met.shape == (4,)
+    assert np.isfinite(gp).all() and np.isfinite(reps).all()
+    assert 0.0 <= met[2] <= 1.0     # Test/Acc of the last round
 
 
 def test_serve_api(tmp_path):
