@@ -118,14 +118,16 @@ __device__ __forceinline__ void opt_update(const TrainArgs& a, int64_t row,
   __syncthreads();
   const int tnew = a.t[row];
   const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+  // 1 - beta as torch rounds it (from double): 1.f - 0.999f is 1.3e-5 short
+  const float omb1 = 0.1f, omb2 = 0.001f;
   const float bc1 = 1.f - powf(b1, (float)tnew);
   const float bc2 = 1.f - powf(b2, (float)tnew);
   const float lr_ = a.lr[row];
   for (int p = tid; p < a.P; p += THREADS) {
     const int64_t gp = row * a.P + p;
     const float gr = grad[p] + a.wd * w[p];
-    const float mn = b1 * a.m[gp] + (1.f - b1) * gr;
-    const float vn = b2 * a.v[gp] + (1.f - b2) * gr * gr;
+    const float mn = b1 * a.m[gp] + omb1 * gr;
+    const float vn = b2 * a.v[gp] + omb2 * gr * gr;
     a.m[gp] = mn;
     a.v[gp] = vn;
     const float vm = fmaxf(a.vmax[gp], vn);
@@ -583,6 +585,10 @@ void apply_aggregate_kernel(float* __restrict__ global_params,
   const int m = blockIdx.x;
   const float tot = partial[(int64_t)m * (P + 1) + P];
   const bool upd = tot > 0.f && !(mask && !mask[m]);
+  // every wave must have loaded `tot` before thread 0 drains the slot;
+  // a wave arriving after the store would otherwise see 0 and skip its
+  // slice of the model while still zeroing its slice of `partial`
+  __syncthreads();
   if (threadIdx.x == 0) {
     totals[m] = tot;
     partial[(int64_t)m * (P + 1) + P] = 0.f;
@@ -979,6 +985,8 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
                      c10::optional<torch::Tensor> partial) {
   const int G = rows.size(0);
   if (G == 0) return;
+  TORCH_CHECK(O >= 1 && O <= 64,
+              "train_fused: O=", O, " outside the per-sample float[64] logits");
   check_f32_2d(params, "params");
   const int P = params.size(1);
   const int E = step_off.size(1);
@@ -1029,6 +1037,8 @@ torch::Tensor eval_tasks_hip(
     torch::Tensor task_row, torch::Tensor task_id, torch::Tensor off,
     torch::Tensor len, int64_t n_tasks, int64_t D, int64_t H, int64_t O,
     int64_t kind, bool want_mse, c10::optional<torch::Tensor> x_mask) {
+  TORCH_CHECK(O >= 1 && O <= 64,
+              "eval_tasks: O=", O, " outside the per-sample float[64] logits");
   const int W = task_row.size(0);
   auto optd = torch::TensorOptions().dtype(torch::kFloat64)
                   .device(params.device());
@@ -1089,6 +1099,8 @@ torch::Tensor ens_vote_multi_hip(
     torch::Tensor y, torch::Tensor task_id, torch::Tensor off,
     torch::Tensor len, int64_t n_tasks, int64_t D, int64_t H, int64_t O,
     int64_t kind, int64_t mode, c10::optional<torch::Tensor> masks) {
+  TORCH_CHECK(O >= 1 && O <= 64,
+              "ens_vote_multi: O=", O, " outside the per-sample float[64] logits");
   const int W = task_id.size(0);
   auto optd = torch::TensorOptions().dtype(torch::kFloat64)
                   .device(params.device());
@@ -1124,6 +1136,8 @@ torch::Tensor confusion_tasks_hip(
     torch::Tensor len, int64_t n_tasks, int64_t n_classes, int64_t D,
     int64_t H, int64_t O, int64_t kind,
     c10::optional<torch::Tensor> masks) {
+  TORCH_CHECK(O >= 1 && O <= 64,
+              "confusion_tasks: O=", O, " outside the per-sample float[64] logits");
   const int W = task_row.size(0);
   auto optd = torch::TensorOptions().dtype(torch::kFloat64)
                   .device(params.device());

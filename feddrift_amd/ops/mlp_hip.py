@@ -33,14 +33,16 @@ _KIND = {"fnn": 0, "lr": 1}
 LDS_BUDGET_FLOATS = 150 * 1024 // 4
 TRAIN_MAX_P = (LDS_BUDGET_FLOATS - 4096) // 2
 EVAL_MAX_P = LDS_BUDGET_FLOATS - 64
+# every MLP kernel keeps one sample's logits in a float[64] register array
+MAX_O = 64
 
 
 def _fits_train(spec: MLPSpec) -> bool:
-    return spec.n_params <= TRAIN_MAX_P
+    return spec.n_params <= TRAIN_MAX_P and spec.o <= MAX_O
 
 
 def _fits_eval(spec: MLPSpec) -> bool:
-    return spec.n_params <= EVAL_MAX_P
+    return spec.n_params <= EVAL_MAX_P and spec.o <= MAX_O
 
 
 def train_fused(spec: MLPSpec, params_all: torch.Tensor, rows: torch.Tensor,
@@ -124,7 +126,7 @@ def ens_vote_multi(spec: MLPSpec, params: torch.Tensor,
     (AUE _infer_ens / AUE-PC per-client weights / KUE soft vote —
     FedAvgEnsAggregatorAue.py:256-283, Kue:234-264). weights [M] or
     per-task [T, M]."""
-    if not _fits_eval(spec) or spec.o > 64:
+    if not _fits_eval(spec):
         return mlp_torch.ens_vote_multi(
             spec, params, weights, x_arena, y_arena, task_id, win_off,
             win_len, n_tasks, mode=mode, masks=masks)
@@ -152,7 +154,7 @@ def confusion_tasks(spec: MLPSpec, params: torch.Tensor,
                     x_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-task confusion matrices in ONE kernel launch (KUE kappa,
     FedAvgEnsAggregatorKue.py:266-303)."""
-    if not _fits_eval(spec) or n_classes != spec.o or spec.o > 64:
+    if not _fits_eval(spec) or n_classes != spec.o:
         return mlp_torch.confusion_tasks(
             spec, params, x_arena, y_arena, task_row, task_id, win_off,
             win_len, n_tasks, n_classes, x_mask=x_mask)

@@ -24,13 +24,15 @@ ADAM_EPS = 1e-8
 
 
 def make_opt_state(kind: str, n_pairs: int, n_params: int, lr: float,
-                   wd: float, device) -> Dict:
-    st = {"kind": kind, "lr": torch.full((n_pairs,), lr, device=device),
+                   wd: float, device, dtype=torch.float32) -> Dict:
+    st = {"kind": kind,
+          "lr": torch.full((n_pairs,), lr, device=device, dtype=dtype),
           "wd": wd}
     if kind == "adam":
-        st["m"] = torch.zeros(n_pairs, n_params, device=device)
-        st["v"] = torch.zeros(n_pairs, n_params, device=device)
-        st["vmax"] = torch.zeros(n_pairs, n_params, device=device)
+        z = dict(device=device, dtype=dtype)
+        st["m"] = torch.zeros(n_pairs, n_params, **z)
+        st["v"] = torch.zeros(n_pairs, n_params, **z)
+        st["vmax"] = torch.zeros(n_pairs, n_params, **z)
         st["t"] = torch.zeros(n_pairs, dtype=torch.int32, device=device)
     return st
 
@@ -84,9 +86,11 @@ def _apply_update(kind: str, lr: torch.Tensor, wd: float, st: Dict,
     st["m"].mul_(ADAM_B1).add_(g, alpha=1 - ADAM_B1)
     st["v"].mul_(ADAM_B2).addcmul_(g, g, value=1 - ADAM_B2)
     torch.maximum(st["vmax"], st["v"], out=st["vmax"])
-    tf = t.float().unsqueeze(-1)
-    bc1 = 1 - torch.pow(torch.tensor(ADAM_B1, device=params.device), tf)
-    bc2 = 1 - torch.pow(torch.tensor(ADAM_B2, device=params.device), tf)
+    tf = t.to(params.dtype).unsqueeze(-1)
+    bc1 = 1 - torch.pow(torch.tensor(ADAM_B1, device=params.device,
+                                     dtype=params.dtype), tf)
+    bc2 = 1 - torch.pow(torch.tensor(ADAM_B2, device=params.device,
+                                     dtype=params.dtype), tf)
     denom = (st["vmax"] / bc2).sqrt_().add_(ADAM_EPS)
     params -= lr * (st["m"] / bc1) / denom
 
@@ -369,7 +373,7 @@ def ens_vote_multi(spec: MLPSpec,
         wt = weights.unsqueeze(0).expand(W, M)
     else:
         wt = weights[task_id]                       # [W, M]
-    votes = torch.zeros(W, bmax, spec.o, device=dev)
+    votes = torch.zeros(W, bmax, spec.o, device=dev, dtype=params.dtype)
     for m in range(M):
         wm = wt[:, m]
         if float(wm.abs().max()) == 0.0:
