@@ -30,14 +30,19 @@ import torch
 
 from . import hip_loader
 
-# CNN_DropOut geometry (must match cnn_kernels.hip)
-X1N = 32 * 26 * 26
-Z2N = 64 * 24 * 24
-NF = 9216
-NH = 128
-D_IN = 784
+# CNN_DropOut geometry, the fc1 K-split count and the eval modes are
+# defined once, in cnn_kernels.hip, and exported by the extension. The
+# engine reads them from its loaded module (self.mod); importing this file
+# does not load the extension (CPU runs import it for is_cnn_dropout).
+# `from cnn_hip import EV_DUMP` and the like resolve here, on first use.
+_EXPORTED = ("X1N", "Z2N", "NF", "NH", "D_IN", "FC1_KS",
+             "EV_ACC", "EV_CONF", "EV_DUMP")
 
-EV_ACC, EV_CONF, EV_DUMP = 0, 1, 2
+
+def __getattr__(name):
+    if name in _EXPORTED:
+        return getattr(hip_loader.load(), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def is_cnn_dropout(module: torch.nn.Module) -> bool:
@@ -53,6 +58,12 @@ class CnnHipEngine:
     # pairs are independent). Sized for 288 GB of HBM3E: bigger chunks =
     # fewer launch sequences per round at FEMNIST-scale fleets.
     WS_BUDGET = 24 << 30
+    # the arena's bytes per (pair, sample) that the chunking budgets for:
+    # fp32 x1, dx1, a2, da2, one more [NF], zz2, z1, a1 and 64 floats of
+    # partials, plus the uint8 pidx. A host-side sizing figure usable
+    # without the extension; __init__ checks it against the kernels'
+    # geometry.
+    WS_BYTES_PER_SAMPLE = 441_600
 
     def __init__(self, template: torch.nn.Module, packer, device):
         assert is_cnn_dropout(template)
@@ -61,7 +72,9 @@ class CnnHipEngine:
         self.device = device
         self.O = template.linear_2.out_features
         self.P = packer.n_params
-        self.mod = hip_loader.load()
+        self.mod = k = hip_loader.load()
+        assert self.WS_BYTES_PER_SAMPLE == 4 * (
+            2 * k.X1N + 3 * k.NF + k.Z2N + 2 * k.NH + 64) + k.NF
         self.dropout_override: Optional[tuple] = None
         self._seed_counter = 0
         self._ws = None
@@ -82,23 +95,24 @@ class CnnHipEngine:
         if ws is not None and ws["G"] >= G and ws["B"] >= B:
             return ws
         dev = self.device
+        k = self.mod
         f = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
         ws = {
             "G": G, "B": B,
-            "x1": f(G * B * X1N),
-            "a2": f(G * B * NF),
-            "pidx": torch.empty(G * B * NF, dtype=torch.uint8, device=dev),
-            "z1": f(G * B * NH),
-            "a1": f(G * B * NH),
+            "x1": f(G * B * k.X1N),
+            "a2": f(G * B * k.NF),
+            "pidx": torch.empty(G * B * k.NF, dtype=torch.uint8, device=dev),
+            "z1": f(G * B * k.NH),
+            "a1": f(G * B * k.NH),
             "dz2": f(G * B * 64),
-            "dz1": f(G * B * NH),
-            "da2": f(G * B * NF),
-            "zz2": f(G * B * Z2N),
-            "dx1": f(G * B * X1N),
+            "dz1": f(G * B * k.NH),
+            "da2": f(G * B * k.NF),
+            "zz2": f(G * B * k.Z2N),
+            "dx1": f(G * B * k.X1N),
             "c1part": f(G * B * 320),
             "wtf": f(G * 9 * 2048),
             "wtd": f(G * 9 * 2048),
-            "z1part": f(G * 8 * B * NH),
+            "z1part": f(G * k.FC1_KS * B * k.NH),
             "w2ms": self._w2ms(G),
             "w2part": f(G * self._w2ms(G) * 9 * 2048),
             "b2part": f(G * B * 64),
@@ -119,8 +133,7 @@ class CnnHipEngine:
         return min(64, max(1, 1024 // max(G, 1)))
 
     def _chunk_pairs(self, B: int) -> int:
-        per_pair = (2 * X1N + 3 * NF + Z2N + 2 * NH + 64) * B * 4 \
-            + NF * B + self.P * 4
+        per_pair = self.WS_BYTES_PER_SAMPLE * B + self.P * 4
         return max(1, min(2048, int(self.WS_BUDGET // max(1, per_pair))))
 
     def train(self, global_params: torch.Tensor, replicas: torch.Tensor,
@@ -210,11 +223,12 @@ class CnnHipEngine:
         confusion accumulation is order-invariant, and the DUMP sink
         receives the chunk's (sorted) window arrays plus per-slot ids."""
         dev = self.device
+        k = self.mod
         W = task_row.numel()
-        if mode == EV_ACC:
+        if mode == k.EV_ACC:
             total_out = torch.zeros(4 if want_mse else 3, n_tasks,
                                     dtype=torch.float64, device=dev)
-        elif mode == EV_CONF:
+        elif mode == k.EV_CONF:
             total_out = torch.zeros(n_tasks, self.O, self.O,
                                     dtype=torch.float64, device=dev)
         else:
@@ -242,18 +256,18 @@ class CnnHipEngine:
                 csum, base + self.EVAL_SLOT_BUDGET, right=True))
             end = max(start + 1, min(W, end_idx))
             tr = task_row[start:end].contiguous()
-            ti = task_id[start:end].contiguous()
-            wo = win_off[start:end].contiguous()
-            wl = win_len[start:end].contiguous()
+            ti = task_id[start:end]
+            wo = win_off[start:end]
+            wl = win_len[start:end]
             slot = torch.cumsum(wl, 0) - wl
             slots = int(wl.sum())
-            max_len = int(wl.max()) if wl.numel() else 0
             if a2e is None or a2e.shape[0] < slots:
-                a2e = torch.empty(max(slots, 1), NF, device=dev)
-                z1e = torch.empty(max(slots, 1), NH, device=dev)
-                z1pe = torch.empty(max(slots, 1), 8 * NH, device=dev)
-                x1e = torch.empty(max(slots, 1), X1N, device=dev)
-                z2e = torch.empty(max(slots, 1), Z2N, device=dev)
+                a2e = torch.empty(max(slots, 1), k.NF, device=dev)
+                z1e = torch.empty(max(slots, 1), k.NH, device=dev)
+                z1pe = torch.empty(max(slots, 1), k.FC1_KS * k.NH,
+                                   device=dev)
+                x1e = torch.empty(max(slots, 1), k.X1N, device=dev)
+                z2e = torch.empty(max(slots, 1), k.Z2N, device=dev)
             # per-slot metadata
             srow = tr.repeat_interleave(wl)
             stid = ti.repeat_interleave(wl)
@@ -270,16 +284,15 @@ class CnnHipEngine:
                 xm = (x_mask[start:end].contiguous()
                       if x_mask.dim() == 2 else x_mask.contiguous())
             outp = None
-            if mode == EV_DUMP:
+            if mode == k.EV_DUMP:
                 outp = torch.empty(slots, self.O, device=dev)
             out = self.mod.cnn_eval(
-                params.contiguous(), tr, ti, wo, wl, slot,
-                self._x_arena, self._y_arena, a2e, z1e, z1pe, x1e, z2e,
-                wtf_e,
+                params.contiguous(), self._x_arena, a2e, z1e, z1pe, x1e,
+                z2e, wtf_e,
                 blk_row, blk_s0, blk_len, srow, stid, sy.contiguous(),
                 soff.contiguous(), swin.contiguous(),
-                xm, n_tasks, self.O, mode, want_mse, max_len, slots, outp)
-            if mode == EV_DUMP:
+                xm, n_tasks, self.O, mode, want_mse, slots, outp)
+            if mode == k.EV_DUMP:
                 dump_sink(stid, sy, outp)
             else:
                 total_out += out
@@ -320,7 +333,7 @@ class CnnHipEngine:
                            **kw) -> torch.Tensor:
         self._x_arena, self._y_arena = x_arena, y_arena
         return self._eval_sweep(params, task_row, task_id, win_off, win_len,
-                                n_tasks, EV_ACC, want_mse=want_mse,
+                                n_tasks, self.mod.EV_ACC, want_mse=want_mse,
                                 x_mask=x_mask)
 
     @torch.no_grad()
@@ -331,7 +344,7 @@ class CnnHipEngine:
         assert n_classes == self.O
         self._x_arena, self._y_arena = x_arena, y_arena
         return self._eval_sweep(params, task_row, task_id, win_off, win_len,
-                                n_tasks, EV_CONF, x_mask=x_mask)
+                                n_tasks, self.mod.EV_CONF, x_mask=x_mask)
 
     @torch.no_grad()
     def vote_multi(self, params: torch.Tensor, weights: torch.Tensor,
@@ -385,7 +398,8 @@ class CnnHipEngine:
                 _w[0] = s0 + ns
 
             self._eval_sweep(params, rowv, task_id, win_off, win_len,
-                             n_tasks, EV_DUMP, x_mask=xm, dump_sink=sink)
+                             n_tasks, self.mod.EV_DUMP, x_mask=xm,
+                             dump_sink=sink)
         tids = torch.cat([slot_meta[k][0] for k in sorted(slot_meta)])
         y = torch.cat([slot_meta[k][1] for k in sorted(slot_meta)])
         pred = votes.argmax(1)

@@ -101,7 +101,8 @@ struct CnnArgs {
 #define OPT_ADAM 1
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define EVAL_BK 32
+#define FC1_BK 32       // fc1 GEMM K-tile depth
+#define FC1_KS 8        // fc1 K-split count (train z1part and eval z1pe)
 
 __device__ __forceinline__ float hash_u01(unsigned long long s,
                                           unsigned long long id) {
@@ -134,29 +135,34 @@ __device__ __forceinline__ long long step_o(const CnnArgs& a, int g) {
 }
 
 // ---------------------------------------------------------------------------
-// forward
+// forward tile bodies, shared by the training kernels (block per (g, b),
+// weights in work[g]) and the eval kernels (block per slot, weights in
+// params[srow[slot]]). A kernel resolves its sample and its pointers and
+// calls the body; the arithmetic exists once.
 // ---------------------------------------------------------------------------
 
-// conv1 forward, block per (g, b): the masked input and the conv1
-// weights stage in LDS once; each thread emits channels-last x1
-// elements (9 fused MACs each). x1 is CHANNELS-LAST [G, B, 676, 32] so
-// the conv2 MFMA stagers read contiguous ci slices.
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_conv1_fwd(CnnArgs a) {
-  const int g = blockIdx.x / a.B;
-  const int b = blockIdx.x - g * a.B;
-  if (b >= step_n(a, g)) return;
+// masked 784-float input row -> LDS (the caller barriers)
+__device__ __forceinline__ void stage_masked_input(float* xin,
+                                                   const float* xs,
+                                                   const float* xm) {
+  for (int d = threadIdx.x; d < D_IN; d += WG)
+    xin[d] = xm ? xs[d] * xm[d] : xs[d];
+}
+
+// conv1 forward for one sample: the masked input and the conv1 weights
+// (w = the model's flat parameter row) stage in LDS once; each thread
+// emits channels-last x1 elements (9 fused MACs each). x1 is
+// CHANNELS-LAST [676, 32] so the conv2 MFMA stagers read contiguous ci
+// slices.
+__device__ __forceinline__ void conv1_fwd_body(const float* xs,
+                                               const float* xm,
+                                               const float* w, float* out) {
   const int tid = threadIdx.x;
   __shared__ __attribute__((aligned(16))) float xin[D_IN];
   __shared__ __attribute__((aligned(16))) float wc[288 + C1];
-  const float* w = a.work + (long long)g * a.P;
-  const float* xs = a.x + (step_o(a, g) + b) * D_IN;
-  const float* xm = a.x_mask ? a.x_mask + (long long)g * D_IN : nullptr;
-  for (int d = tid; d < D_IN; d += WG)
-    xin[d] = xm ? xs[d] * xm[d] : xs[d];
+  stage_masked_input(xin, xs, xm);
   for (int i = tid; i < 288 + C1; i += WG) wc[i] = w[OFF_W1C + i];
   __syncthreads();
-  float* out = a.x1 + ((long long)g * a.B + b) * X1N;
   for (int e = tid; e < X1N; e += WG) {
     const int pp = e / C1;
     const int c = e - pp * C1;
@@ -172,129 +178,54 @@ void cnn_conv1_fwd(CnnArgs a) {
   }
 }
 
-// reshape conv2 weights for the MFMA stagers (per pair, per epoch):
-// wtf[g][kyx][ci][co] (fwd B-operand) and wtd[g][kyx][co][ci] (dgrad)
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_w2_reshape(CnnArgs a) {
-  const long long total = (long long)a.G * C2 * C1 * 9;
-  for (long long q = (long long)blockIdx.x * WG + threadIdx.x; q < total;
-       q += (long long)gridDim.x * WG) {
-    const int g = (int)(q / (C2 * C1 * 9));
-    const int r = (int)(q - (long long)g * C2 * C1 * 9);
-    const int co = r / (C1 * 9);
-    const int t = r - co * C1 * 9;
-    const int ci = t / 9;
-    const int kyx = t - ci * 9;
-    const float wv = a.work[(long long)g * a.P + OFF_W2C + r];
-    a.wtf[((long long)g * 9 + kyx) * 2048 + ci * C2 + co] = wv;
-    a.wtd[((long long)g * 9 + kyx) * 2048 + co * C1 + ci] = wv;
-  }
-}
-
-// conv2 forward as implicit GEMM on f32 MFMA: per (g, b, ptile) block,
-// 64 output pixels x 64 channels, K = 9 taps x 32 ci. The x1 REGION
-// feeding all 9 taps (6 rows x 26 cols x 32 ci, channels-last) stages
-// once per block — ONE barrier, then 288 MFMAs with the B operand
-// (reshaped weights, L2-resident: 74 KB per pair shared by 9*B blocks)
-// loaded straight to registers. z2 lands CHANNELS-LAST in zz2.
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_conv2_fwd_mfma(CnnArgs a) {
-  const int pt = blockIdx.x % 9;           // 576 / 64
-  const int gb = blockIdx.x / 9;
-  const int g = gb / a.B;
-  const int b = gb - g * a.B;
-  if (b >= step_n(a, g)) return;
+// conv2 forward as implicit GEMM on f32 MFMA: one tile of 64 * MF output
+// pixels x 64 channels of one sample, K = 9 taps x 32 ci; each wave owns
+// MF 16-pixel M-fragments. The x1 REGION feeding all 9 taps (6 or 8
+// rows x 26 cols x 32 ci, channels-last) stages once per block — ONE
+// barrier, then the MFMAs with the B operand (reshaped weights wt
+// [9][32][64], L2-resident: 74 KB per model shared by all its blocks)
+// loaded straight to registers. z2 lands CHANNELS-LAST.
+//   MF = 1: 64-pixel tiles, 9 per sample, 6-row region.
+//   MF = 2: 128-pixel tiles, 5 per sample, 8-row region (27.5 KB LDS):
+//           every weight load feeds two MFMAs and each wave runs eight
+//           accumulator chains; the last tile is partial (pp < 576).
+template <int MF>
+__device__ __forceinline__ void conv2_fwd_body(const float* x1_sample,
+                                               const float* wt,
+                                               const float* bias,
+                                               float* z2, int pt) {
+  constexpr int ROWS = MF == 1 ? 6 : 8;
   const int tid = threadIdx.x;
   const int wv = tid >> 6;
   const int l = tid & 63;
   const int li = l & 15, lk = l >> 4;
-  // region: x1 rows [r0, r0+6) x 26 cols, channels-last, +1 padded
-  __shared__ __attribute__((aligned(16))) float sR[6 * S1][C1 + 1];
-  const int p0 = pt * 64;
+  // region: x1 rows [r0, r0+ROWS) x 26 cols, channels-last, +1 padded
+  __shared__ __attribute__((aligned(16))) float sR[ROWS * S1][C1 + 1];
+  const int p0 = pt * (64 * MF);
   const int r0 = p0 / S2;
-  const float* x1 = a.x1 + (((long long)g * a.B + b) * 676
-                            + (long long)r0 * S1) * C1;
+  const float* x1 = x1_sample + (long long)r0 * S1 * C1;
   {
     // last tile: x1 only has rows r0..25 — rows past it are never read
     // by the compute (oy <= 25) but must not be FETCHED (OOB)
-    const int nrow = min(6 * S1, (S1 - r0) * S1);
+    const int nrow = min(ROWS * S1, (S1 - r0) * S1);
     const int r8 = tid >> 5, kk = tid & 31;
-    for (int rr = r8; rr < 6 * S1; rr += 8)
+    for (int rr = r8; rr < ROWS * S1; rr += 8)
       sR[rr][kk] = (rr < nrow) ? x1[(long long)rr * C1 + kk] : 0.f;
   }
   __syncthreads();
-  f32x4 acc[4];
+  f32x4 acc[MF][4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-  // this lane's A row: output pixel p = p0 + wv*16 + li
-  const int p = p0 + wv * 16 + li;
-  const int arow = (p / S2 - r0) * S1 + (p - (p / S2) * S2);
-  const float* wt = a.wtf + (long long)g * 9 * 2048;
-  for (int kyx = 0; kyx < 9; ++kyx) {
-    const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
-    const int off = arow + ky * S1 + kx;
-    const float* wk = wt + kyx * 2048;
-#pragma unroll
-    for (int ks = 0; ks < C1 / 4; ++ks) {
-      const float av = sR[off][ks * 4 + lk];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            av, wk[(ks * 4 + lk) * C2 + ct * 16 + li], acc[ct], 0, 0, 0);
-    }
-  }
-  const float* bias = a.work + (long long)g * a.P + OFF_B2C;
-  float* z2 = a.zz2 + ((long long)g * a.B + b) * Z2N;
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int co = ct * 16 + li;
-    const float bb = bias[co];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int pp = p0 + wv * 16 + lk * 4 + r;
-      z2[(long long)pp * C2 + co] = acc[ct][r] + bb;
-    }
-  }
-}
-
-// conv2 forward, 128-pixel tiles (the dgrad-v3 trick applied to fwd):
-// each wave owns TWO 16-pixel M-fragments, so every weight load feeds
-// two MFMAs (fwd was issue-stalled 0.65 with one global per MFMA) and
-// each wave runs eight accumulator chains. Region = 8 input rows,
-// 27.5 KB LDS.
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_conv2_fwd_mfma2(CnnArgs a) {
-  const int pt = blockIdx.x % 5;           // ceil(576 / 128)
-  const int gb = blockIdx.x / 5;
-  const int g = gb / a.B;
-  const int b = gb - g * a.B;
-  if (b >= step_n(a, g)) return;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const int l = tid & 63;
-  const int li = l & 15, lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sR[8 * S1][C1 + 1];
-  const int p0 = pt * 128;
-  const int r0 = p0 / S2;
-  const float* x1 = a.x1 + (((long long)g * a.B + b) * 676
-                            + (long long)r0 * S1) * C1;
-  {
-    const int nrow = min(8 * S1, (S1 - r0) * S1);
-    const int r8 = tid >> 5, kk = tid & 31;
-    for (int rr = r8; rr < 8 * S1; rr += 8)
-      sR[rr][kk] = (rr < nrow) ? x1[(long long)rr * C1 + kk] : 0.f;
-  }
-  __syncthreads();
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int mf = 0; mf < 2; ++mf)
+  for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[mf][t] = {0.f, 0.f, 0.f, 0.f};
-  const int p_a = p0 + wv * 32 + li;
+  // this lane's A rows: output pixel p_a (M-fragment 0) and p_b (1).
+  // Per-fragment values are named scalars, not MF-sized arrays: small
+  // private arrays in the tap loop change how the compiler unrolls it
+  // and the weight loads lose their scalar-base addressing.
+  const int p_a = p0 + wv * (16 * MF) + li;
   const int p_b = p_a + 16;
   const int arow_a = (p_a / S2 - r0) * S1 + (p_a - (p_a / S2) * S2);
   const int arow_b = (p_b / S2 - r0) * S1 + (p_b - (p_b / S2) * S2);
-  const float* wt = a.wtf + (long long)g * 9 * 2048;
   for (int kyx = 0; kyx < 9; ++kyx) {
     const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
     const int offa = arow_a + ky * S1 + kx;
@@ -303,52 +234,45 @@ void cnn_conv2_fwd_mfma2(CnnArgs a) {
 #pragma unroll
     for (int ks = 0; ks < C1 / 4; ++ks) {
       const float av0 = sR[offa][ks * 4 + lk];
-      const float av1 = sR[offb][ks * 4 + lk];
+      float av1 = 0.f;
+      if constexpr (MF == 2) av1 = sR[offb][ks * 4 + lk];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
-        const float wv_ = wk[(ks * 4 + lk) * C2 + ct * 16 + li];
-        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0, wv_,
-                                                          acc[0][ct],
-                                                          0, 0, 0);
-        acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1, wv_,
-                                                          acc[1][ct],
-                                                          0, 0, 0);
+        const float bv = wk[(ks * 4 + lk) * C2 + ct * 16 + li];
+        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            av0, bv, acc[0][ct], 0, 0, 0);
+        if constexpr (MF == 2)
+          acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              av1, bv, acc[1][ct], 0, 0, 0);
       }
     }
   }
-  const float* bias = a.work + (long long)g * a.P + OFF_B2C;
-  float* z2 = a.zz2 + ((long long)g * a.B + b) * Z2N;
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
     const int co = ct * 16 + li;
     const float bb = bias[co];
 #pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
+    for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int pp = p0 + wv * 32 + mf * 16 + lk * 4 + r;
-        if (pp < Z2N / C2)
+        const int pp = p0 + (wv * MF + mf) * 16 + lk * 4 + r;
+        if (MF == 1 || pp < Z2N / C2)
           z2[(long long)pp * C2 + co] = acc[mf][ct][r] + bb;
       }
   }
 }
 
-// maxpool + dropout1 over the channels-last z2, block per (g, b):
-// z2 rows stage through LDS (coalesced channels-last reads), the pooled
-// a2/pidx tiles assemble in LDS and store with one coalesced pass in the
-// torch-flatten [c][py][px] layout
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_pool_fwd(CnnArgs a) {
-  const int g = blockIdx.x / a.B;
-  const int b = blockIdx.x - g * a.B;
-  if (b >= step_n(a, g)) return;
+// 2x2 maxpool of one sample's channels-last z2 into sa2 (LDS, [NF] in
+// the torch-flatten [c][py][px] layout): z2 row pairs stage through LDS
+// double-buffered (coalesced channels-last reads) — the next pooled
+// row's loads issue before this row's max pass, land after it. TRAIN
+// also records the argmax (first maximum wins: strict >) in spidx; eval
+// keeps the max only. Returns after the barrier that publishes sa2.
+template <bool TRAIN>
+__device__ __forceinline__ void pool_rows_body(const float* z2, float* sa2,
+                                               unsigned char* spidx) {
   const int tid = threadIdx.x;
   __shared__ __attribute__((aligned(16))) float srow[2][2 * S2 * C2];
-  __shared__ __attribute__((aligned(16))) float sa2[NF];
-  __shared__ unsigned char spidx[NF];
-  const float* z2 = a.zz2 + ((long long)g * a.B + b) * Z2N;
-  // double-buffered row-pair staging: the next pooled row's z2 loads
-  // issue before this row's max pass, land after it
   float rst[12];
 #define PF_LOAD(py)                                                     \
   _Pragma("unroll") for (int jj = 0; jj < 12; ++jj)                      \
@@ -372,10 +296,14 @@ void cnn_pool_fwd(CnnArgs a) {
 #pragma unroll
         for (int dx = 0; dx < 2; ++dx) {
           const float z = srow[cur][(dy * S2 + 2 * px + dx) * C2 + c];
-          if (z > best) { best = z; arg = dy * 2 + dx; }
+          if (TRAIN) {
+            if (z > best) { best = z; arg = dy * 2 + dx; }
+          } else {
+            best = fmaxf(best, z);
+          }
         }
       sa2[c * (SP * SP) + py * SP + px] = best;
-      spidx[c * (SP * SP) + py * SP + px] = (unsigned char)arg;
+      if (TRAIN) spidx[c * (SP * SP) + py * SP + px] = (unsigned char)arg;
     }
     if (py + 1 < SP) { PF_WRITE(cur ^ 1); }
     __syncthreads();
@@ -383,47 +311,35 @@ void cnn_pool_fwd(CnnArgs a) {
   }
 #undef PF_LOAD
 #undef PF_WRITE
-  float* a2o = a.a2 + ((long long)g * a.B + b) * NF;
-  unsigned char* po = a.pidx + ((long long)g * a.B + b) * NF;
-  for (int e = tid; e < NF; e += WG) {
-    a2o[e] = sa2[e] * drop_scale(a, 0, g, b, e);
-    po[e] = spidx[e];
-  }
 }
 
-// fc1 forward as MFMA GEMM with K split over blocks (fills the chip at
-// small fleets): block (g, mtile, ks) computes partial z1 for 64 batch
-// rows x 128 h over K-range [ks*NF/KS, ...). Partials land in z1part.
-#define FC1_KS 8
-
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_fc1_fwd_mfma(CnnArgs a) {
-  const int mtiles = (a.B + 63) / 64;
-  const int ks = blockIdx.x % FC1_KS;
-  const int rest = blockIdx.x / FC1_KS;
-  const int mt = rest % mtiles;
-  const int g = rest / mtiles;
-  const int n = step_n(a, g);
-  if (mt * 64 >= n) return;
+// fc1 as an MFMA tile GEMM with K split over blocks (fills the chip at
+// small fleets and small eval sweeps): partial z1 for up to 64 rows of A
+// (mlen live, row stride NF) x 128 h over K-range [k_lo, k_hi) against
+// the fc1 weight wp [128][NF]. 4 waves x 16 rows x 128 cols, f32-input
+// MFMA, BK = 32 double-buffered register-staged LDS tiles with +1
+// padding (issue the next tile's loads before the MFMAs, write after).
+// Row r of the partial lands at out + r * out_stride.
+__device__ __forceinline__ void fc1_tile_body(const float* A_rows, int mlen,
+                                              const float* wp, int k_lo,
+                                              int k_hi, float* out,
+                                              long long out_stride) {
   const int tid = threadIdx.x;
   const int wv = tid >> 6;
   const int l = tid & 63;
   const int li = l & 15, lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sA[2][64][EVAL_BK + 1];
-  __shared__ __attribute__((aligned(16))) float sB[2][EVAL_BK][NH + 1];
+  __shared__ __attribute__((aligned(16))) float sA[2][64][FC1_BK + 1];
+  __shared__ __attribute__((aligned(16))) float sB[2][FC1_BK][NH + 1];
   f32x4 acc[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-  const float* wp = a.work + (long long)g * a.P + OFF_W1F;
-  const float* a2 = a.a2 + ((long long)g * a.B + (long long)mt * 64) * NF;
-  const int mlen = min(64, n - mt * 64);
   const int r8 = tid >> 5, kk = tid & 31;
-  const int k_lo = ks * (NF / FC1_KS), k_hi = (ks + 1) * (NF / FC1_KS);
+  // register staging: 8 A rows + 16 B rows per thread per tile
   float ra[8], rb[16];
 #define FC_LOAD(k0)                                                     \
   _Pragma("unroll") for (int j = 0; j < 8; ++j) {                        \
     const int rr = r8 + j * 8;                                           \
-    ra[j] = (rr < mlen) ? a2[(long long)rr * NF + (k0) + kk] : 0.f;      \
+    ra[j] = (rr < mlen) ? A_rows[(long long)rr * NF + (k0) + kk] : 0.f;  \
   }                                                                      \
   _Pragma("unroll") for (int j = 0; j < 16; ++j)                         \
     rb[j] = wp[(long long)(r8 + j * 8) * NF + (k0) + kk];
@@ -436,17 +352,17 @@ void cnn_fc1_fwd_mfma(CnnArgs a) {
   FC_WRITE(0);
   __syncthreads();
   int cur = 0;
-  for (int k0 = k_lo; k0 < k_hi; k0 += EVAL_BK) {
-    if (k0 + EVAL_BK < k_hi) { FC_LOAD(k0 + EVAL_BK); }
+  for (int k0 = k_lo; k0 < k_hi; k0 += FC1_BK) {
+    if (k0 + FC1_BK < k_hi) { FC_LOAD(k0 + FC1_BK); }
 #pragma unroll
-    for (int kq = 0; kq < EVAL_BK / 4; ++kq) {
+    for (int kq = 0; kq < FC1_BK / 4; ++kq) {
       const float av = sA[cur][wv * 16 + li][kq * 4 + lk];
 #pragma unroll
       for (int ct = 0; ct < 8; ++ct)
         acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
             av, sB[cur][kq * 4 + lk][ct * 16 + li], acc[ct], 0, 0, 0);
     }
-    if (k0 + EVAL_BK < k_hi) { FC_WRITE(cur ^ 1); }
+    if (k0 + FC1_BK < k_hi) { FC_WRITE(cur ^ 1); }
     __syncthreads();
     cur ^= 1;
   }
@@ -457,13 +373,154 @@ void cnn_fc1_fwd_mfma(CnnArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int mrow = wv * 16 + lk * 4 + r;
-      if (mrow < mlen) {
-        const long long b = (long long)mt * 64 + mrow;
-        a.z1part[(((long long)g * FC1_KS + ks) * a.B + b) * NH
-                 + ct * 16 + li] = acc[ct][r];
-      }
+      if (mrow < mlen)
+        out[mrow * out_stride + ct * 16 + li] = acc[ct][r];
     }
   }
+}
+
+// fold the FC1_KS fc1 partials of one (row, h) onto the bias: part
+// points at the ks = 0 partial, consecutive partials lie ks_stride apart
+__device__ __forceinline__ float fc1_fold(float bias, const float* part,
+                                          long long ks_stride) {
+  float z = bias;
+#pragma unroll
+  for (int ks = 0; ks < FC1_KS; ++ks) z += part[ks * ks_stride];
+  return z;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// fc2 + in-graph softmax for one sample on ONE WAVE: from the 128-float
+// activation row a1 and the model's flat parameter row w, returns the
+// model output s[l] in lane l (0 in lanes l >= O). Lane l collects logit
+// l (O <= 64 always): the a1 row loads once into two coalesced registers
+// per lane, each o-round is two coalesced weight loads + two fmas + a
+// wave reduce, and the softmax runs as 6-step shuffle reductions — no
+// per-thread O-arrays (the thread-per-sample form kept z2/s/ds[64] in
+// scratch: 133 us/dispatch of spill traffic at the config-3 probe shape).
+__device__ __forceinline__ float head_softmax(const float* a1,
+                                              const float* w, int O,
+                                              int l) {
+  const float r0 = a1[l], r1 = a1[64 + l];
+  float zlane = 0.f;
+  for (int o = 0; o < O; ++o) {
+    const float* wo = w + OFF_W2F + (long long)o * NH;
+    const float v = wave_sum(fmaf(r0, wo[l], r1 * wo[64 + l]));
+    if (l == o) zlane = v;
+  }
+  const bool live = l < O;
+  const float z = live ? zlane + w[OFF_W2F + (long long)O * NH + l]
+                       : -1e30f;
+  const float zmax = wave_max(z);
+  const float e = live ? __expf(z - zmax) : 0.f;
+  return e / wave_sum(e);
+}
+
+// ---------------------------------------------------------------------------
+// forward (training)
+// ---------------------------------------------------------------------------
+
+// conv1 forward, block per (g, b) -> x1 [G, B, 676, 32]
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_conv1_fwd(CnnArgs a) {
+  const int g = blockIdx.x / a.B;
+  const int b = blockIdx.x - g * a.B;
+  if (b >= step_n(a, g)) return;
+  conv1_fwd_body(a.x + (step_o(a, g) + b) * D_IN,
+                 a.x_mask ? a.x_mask + (long long)g * D_IN : nullptr,
+                 a.work + (long long)g * a.P,
+                 a.x1 + ((long long)g * a.B + b) * X1N);
+}
+
+// reshape conv2 weights for the MFMA stagers (per pair, per epoch):
+// wtf[g][kyx][ci][co] (fwd B-operand) and wtd[g][kyx][co][ci] (dgrad)
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_w2_reshape(CnnArgs a) {
+  const long long total = (long long)a.G * C2 * C1 * 9;
+  for (long long q = (long long)blockIdx.x * WG + threadIdx.x; q < total;
+       q += (long long)gridDim.x * WG) {
+    const int g = (int)(q / (C2 * C1 * 9));
+    const int r = (int)(q - (long long)g * C2 * C1 * 9);
+    const int co = r / (C1 * 9);
+    const int t = r - co * C1 * 9;
+    const int ci = t / 9;
+    const int kyx = t - ci * 9;
+    const float wv = a.work[(long long)g * a.P + OFF_W2C + r];
+    a.wtf[((long long)g * 9 + kyx) * 2048 + ci * C2 + co] = wv;
+    a.wtd[((long long)g * 9 + kyx) * 2048 + co * C1 + ci] = wv;
+  }
+}
+
+// conv2 forward, block per (g, b, ptile): z2 lands in zz2. The 64-pixel
+// kernel is the default; the 128-pixel one (FEDDRIFT_CONV2FWD=2) applies
+// the dgrad-v3 trick to fwd (fwd was issue-stalled 0.65 with one global
+// load per MFMA) and measured slower.
+template <int MF>
+__device__ __forceinline__ void conv2_fwd_train(const CnnArgs& a) {
+  constexpr int TILES = MF == 1 ? 9 : 5;      // ceil(576 / (64 * MF))
+  const int pt = blockIdx.x % TILES;
+  const int gb = blockIdx.x / TILES;
+  const int g = gb / a.B;
+  const int b = gb - g * a.B;
+  if (b >= step_n(a, g)) return;
+  conv2_fwd_body<MF>(a.x1 + ((long long)g * a.B + b) * X1N,
+                     a.wtf + (long long)g * 9 * 2048,
+                     a.work + (long long)g * a.P + OFF_B2C,
+                     a.zz2 + ((long long)g * a.B + b) * Z2N, pt);
+}
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_conv2_fwd_mfma(CnnArgs a) { conv2_fwd_train<1>(a); }
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_conv2_fwd_mfma2(CnnArgs a) { conv2_fwd_train<2>(a); }
+
+// maxpool + dropout1 over the channels-last z2, block per (g, b): the
+// pooled a2/pidx tiles assemble in LDS and store with one coalesced pass
+// in the torch-flatten [c][py][px] layout
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_pool_fwd(CnnArgs a) {
+  const int g = blockIdx.x / a.B;
+  const int b = blockIdx.x - g * a.B;
+  if (b >= step_n(a, g)) return;
+  __shared__ __attribute__((aligned(16))) float sa2[NF];
+  __shared__ unsigned char spidx[NF];
+  pool_rows_body<true>(a.zz2 + ((long long)g * a.B + b) * Z2N, sa2, spidx);
+  float* a2o = a.a2 + ((long long)g * a.B + b) * NF;
+  unsigned char* po = a.pidx + ((long long)g * a.B + b) * NF;
+  for (int e = threadIdx.x; e < NF; e += WG) {
+    a2o[e] = sa2[e] * drop_scale(a, 0, g, b, e);
+    po[e] = spidx[e];
+  }
+}
+
+// fc1 forward: block (g, mtile, ks) computes partial z1 for 64 batch
+// rows x 128 h over K-range [ks*NF/KS, ...). Partials land in z1part
+// [G, FC1_KS, B, NH].
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_fc1_fwd_mfma(CnnArgs a) {
+  const int mtiles = (a.B + 63) / 64;
+  const int ks = blockIdx.x % FC1_KS;
+  const int rest = blockIdx.x / FC1_KS;
+  const int mt = rest % mtiles;
+  const int g = rest / mtiles;
+  const int n = step_n(a, g);
+  if (mt * 64 >= n) return;
+  fc1_tile_body(
+      a.a2 + ((long long)g * a.B + (long long)mt * 64) * NF,
+      min(64, n - mt * 64), a.work + (long long)g * a.P + OFF_W1F,
+      ks * (NF / FC1_KS), (ks + 1) * (NF / FC1_KS),
+      a.z1part + (((long long)g * FC1_KS + ks) * a.B + (long long)mt * 64)
+                     * NH,
+      NH);
 }
 
 // combine fc1 K-split partials + bias, apply relu + dropout2
@@ -477,10 +534,10 @@ void cnn_fc1_act(CnnArgs a) {
     const int b = (int)(r / NH);
     if (b >= step_n(a, g)) continue;
     const int h = (int)(r - (long long)b * NH);
-    float z = a.work[(long long)g * a.P + OFF_B1F + h];
-#pragma unroll
-    for (int ks = 0; ks < FC1_KS; ++ks)
-      z += a.z1part[(((long long)g * FC1_KS + ks) * a.B + b) * NH + h];
+    const float z = fc1_fold(
+        a.work[(long long)g * a.P + OFF_B1F + h],
+        a.z1part + ((long long)g * FC1_KS * a.B + b) * NH + h,
+        (long long)a.B * NH);
     a.z1[q] = z;
     const float rl = z > 0.f ? z : 0.f;
     a.a1[q] = rl * drop_scale(a, 1, g, b, h);
@@ -489,23 +546,8 @@ void cnn_fc1_act(CnnArgs a) {
 
 // fc2 + softmax (in-graph model output s) + CE-on-s gradient -> dz2
 // dL/ds = (softmax(s) - onehot(y)) / n; dL/dz2 = s*(dL/ds - sum(dL/ds*s))
-//
-// ONE WAVE per sample: lane l accumulates logit l (O <= 64 always), the
-// a1 row loads once into two coalesced registers per lane, and both
-// softmaxes run as 6-step shuffle reductions — no per-thread O-arrays
-// (the previous thread-per-sample form kept z2/s/ds[64] in scratch:
-// 133 us/dispatch of spill traffic at the config-3 probe shape).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
+// ONE WAVE per sample (head_softmax); the second softmax and the
+// gradient run as the same shuffle reductions.
 extern "C" __global__ __launch_bounds__(WG)
 void cnn_head_fwd(CnnArgs a) {
   const long long total = (long long)a.G * a.B;
@@ -517,23 +559,10 @@ void cnn_head_fwd(CnnArgs a) {
     const int n = step_n(a, g);
     if (b >= n) continue;
     const float inv_n = 1.f / (float)n;
-    const float* w = a.work + (long long)g * a.P;
-    const float* a1 = a.a1 + q * NH;
     const int yi = (int)a.y[step_o(a, g) + b];
-    const float r0 = a1[l], r1 = a1[64 + l];
-    // lane o collects logit o: each o-round is two coalesced weight
-    // loads + two fmas + a wave reduce
-    float zlane = 0.f;
-    for (int o = 0; o < a.O; ++o) {
-      const float* wo = w + OFF_W2F + (long long)o * NH;
-      const float v = wave_sum(fmaf(r0, wo[l], r1 * wo[64 + l]));
-      if (l == o) zlane = v;
-    }
     const bool live = l < a.O;
-    float z = live ? zlane + w[OFF_W2F + (long long)a.O * NH + l] : -1e30f;
-    const float zmax = wave_max(z);
-    float e = live ? __expf(z - zmax) : 0.f;
-    const float s = e / wave_sum(e);               // model output s[l]
+    const float s = head_softmax(a.a1 + q * NH,
+                                 a.work + (long long)g * a.P, a.O, l);
     // CE(log_softmax(s), y): q2 = softmax(s)
     const float smax = wave_max(live ? s : -1e30f);
     float e2 = live ? __expf(s - smax) : 0.f;
@@ -1062,20 +1091,29 @@ void cnn_conv2_dgrad_mfma(CnnArgs a) {
 #undef DG_ISSUE
 }
 
-// conv2 dgrad v2 — the fwd-shaped decomposition: ONE block per
-// (g, b, mtile of 11), mirroring cnn_conv2_fwd_mfma. The block's 6-row
-// dz region (37 KB, zero-bordered, +1-padded) stages once with ordinary
-// loads and ONE barrier; the B operand (wtd, 74 KB per pair) reads
-// straight from L2 inside the MFMA loop exactly like fwd's wtf. v1
-// keeps everything (weights + region) LDS-resident via the glds DMA
-// pipeline, which is elegant but needs 144 KB of LDS -> ONE block
-// (4 waves) per CU, and its inter-tile barrier + vmcnt waits run
-// unhidden (PMC: 57% parked, profiles/pmc5_summary.json). This shape
-// fits 4 blocks/CU, so parked time overlaps across blocks.
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_conv2_dgrad_mfma2(CnnArgs a) {
-  const int mt = blockIdx.x % 11;
-  const int gb = blockIdx.x / 11;
+// conv2 dgrad v2/v3 — the fwd-shaped decomposition: ONE block per
+// (g, b, mtile), mirroring conv2_fwd_body; each wave owns MF 16-pixel
+// M-fragments. The block's dz region (zero-bordered, +4-padded) stages
+// once with ordinary loads and ONE barrier; the B operand (wtd, 74 KB
+// per pair) reads straight from L2 inside the MFMA loop exactly like
+// fwd's wtf. v1 keeps everything (weights + region) LDS-resident via
+// the glds DMA pipeline, which is elegant but needs 144 KB of LDS ->
+// ONE block (4 waves) per CU, and its inter-tile barrier + vmcnt waits
+// run unhidden (PMC: 57% parked, profiles/pmc5_summary.json). These
+// shapes fit several blocks per CU, so parked time overlaps across
+// blocks.
+//   MF = 1 (v2): 64-pixel tiles, 11 per sample, 6-row region (37 KB,
+//                4 blocks/CU).
+//   MF = 2 (v3): 128-pixel tiles, 6 per sample, 8-row region (52 KB,
+//                3 blocks/CU): every weight load feeds two MFMAs (the B
+//                operand is the per-MFMA global-issue cost in v2) and
+//                each wave runs four independent accumulator chains.
+template <int MF>
+__device__ __forceinline__ void conv2_dgrad_body(const CnnArgs& a) {
+  constexpr int TILES = MF == 1 ? 11 : 6;     // ceil(676 / (64 * MF))
+  constexpr int ROWS = MF == 1 ? 6 : 8;
+  const int mt = blockIdx.x % TILES;
+  const int gb = blockIdx.x / TILES;
   const int g = gb / a.B;
   const int b = gb - g * a.B;
   if (b >= step_n(a, g)) return;
@@ -1086,15 +1124,17 @@ void cnn_conv2_dgrad_mfma2(CnnArgs a) {
   // row stride C2+4 = 68 === 4 (mod 32): the MFMA-loop read
   // sD[arow][ks*4+lk] with arow consecutive in li then hits bank
   // 4*li + lk -- an exact 2-way spread (the 64-lane minimum)
-  __shared__ __attribute__((aligned(16))) float sD[6 * S2][C2 + 4];
+  __shared__ __attribute__((aligned(16))) float sD[ROWS * S2][C2 + 4];
   const float* dz = a.zz2 + ((long long)g * a.B + b) * Z2N;
   const float* wt = a.wtd + (long long)g * 9 * 2048;
   float* dx1 = a.dx1 + ((long long)g * a.B + b) * X1N;
-  const int p0 = mt * 64;
+  const int p0 = mt * (64 * MF);
   const int y0 = p0 / S1;          // first dx1 pixel row of this tile
-  // region = dz rows [y0-2, y0+4): every valid tap of pixels y in
-  // [y0, y0+2] lands inside; rows outside [0, S2) stage as zeros
-  for (int e = tid; e < 6 * S2 * C2; e += WG) {
+  // region = dz rows [y0-2, y0-2+ROWS): the tile's pixels span rows
+  // [y0, y0+2] (MF = 1) or [y0, y0+5] (MF = 2) and taps reach two rows
+  // up, so every valid tap lands inside; rows outside [0, S2) stage as
+  // zeros
+  for (int e = tid; e < ROWS * S2 * C2; e += WG) {
     const int rr = e / (S2 * C2);
     const int rem = e - rr * S2 * C2;
     const int cc = rem / C2;
@@ -1105,123 +1145,68 @@ void cnn_conv2_dgrad_mfma2(CnnArgs a) {
             ? dz[((long long)dzrow * S2 + cc) * C2 + ch] : 0.f;
   }
   __syncthreads();
-  const int p = p0 + wv * 16 + li;        // this lane's dx1 pixel
-  const int y = p / S1, x = p - (p / S1) * S1;
-  f32x4 acc[2];
-  acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-  acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kyx = 0; kyx < 9; ++kyx) {
-    const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
-    const int oy = y - ky, ox = x - kx;
-    // x borders (S1=26 > S2=24) still need operand predication; the
-    // staged y borders are already zero
-    const bool ok = oy >= 0 && oy < S2 && ox >= 0 && ox < S2;
-    const int arow = ok ? (oy - y0 + 2) * S2 + ox : 0;
-    const float* wk = wt + kyx * 2048;
-#pragma unroll
-    for (int ks = 0; ks < C2 / 4; ++ks) {
-      const int co = ks * 4 + lk;
-      float av = sD[arow][co];
-      av = ok ? av : 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            av, wk[co * C1 + ct * 16 + li], acc[ct], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int pix = p0 + wv * 16 + lk * 4 + r;
-      if (pix < 676)
-        dx1[(long long)pix * C1 + ct * 16 + li] = acc[ct][r];
-    }
-}
-
-// conv2 dgrad v3 — v2 with 128-pixel tiles: each wave owns TWO
-// 16-pixel M-fragments, so every weight load feeds two MFMAs (the B
-// operand is the per-MFMA global-issue cost in v2) and each wave runs
-// four independent accumulator chains. Region = 8 dz rows (52 KB,
-// 3 blocks/CU).
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_conv2_dgrad_mfma3(CnnArgs a) {
-  const int mt = blockIdx.x % 6;          // 676 / 128 -> 6 tiles
-  const int gb = blockIdx.x / 6;
-  const int g = gb / a.B;
-  const int b = gb - g * a.B;
-  if (b >= step_n(a, g)) return;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const int l = tid & 63;
-  const int li = l & 15, lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sD[8 * S2][C2 + 4];
-  const float* dz = a.zz2 + ((long long)g * a.B + b) * Z2N;
-  const float* wt = a.wtd + (long long)g * 9 * 2048;
-  float* dx1 = a.dx1 + ((long long)g * a.B + b) * X1N;
-  const int p0 = mt * 128;
-  const int y0 = p0 / S1;
-  // region = dz rows [y0-2, y0+6): pixels y in [y0, y0+5], taps reach
-  // oy in [y0-2, y0+5]; rows outside [0, S2) stage as zeros
-  for (int e = tid; e < 8 * S2 * C2; e += WG) {
-    const int rr = e / (S2 * C2);
-    const int rem = e - rr * S2 * C2;
-    const int cc = rem / C2;
-    const int ch = rem - cc * C2;
-    const int dzrow = y0 - 2 + rr;
-    sD[rr * S2 + cc][ch] =
-        (dzrow >= 0 && dzrow < S2)
-            ? dz[((long long)dzrow * S2 + cc) * C2 + ch] : 0.f;
-  }
-  __syncthreads();
-  const int p_a = p0 + wv * 32 + li;       // M-fragment 0
-  const int p_b = p_a + 16;                // M-fragment 1
+  // this lane's dx1 pixels: p_a (M-fragment 0) and p_b (1); named
+  // scalars, not MF-sized arrays (see conv2_fwd_body)
+  const int p_a = p0 + wv * (16 * MF) + li;
+  const int p_b = p_a + 16;
   const int ya = p_a / S1, xa = p_a - ya * S1;
   const int yb = p_b / S1, xb = p_b - yb * S1;
-  f32x4 acc[2][2];
+  f32x4 acc[MF][2];
 #pragma unroll
-  for (int mf = 0; mf < 2; ++mf)
+  for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) acc[mf][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int kyx = 0; kyx < 9; ++kyx) {
     const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
+    // x borders (S1=26 > S2=24) still need operand predication; the
+    // staged y borders are already zero
     const int oya = ya - ky, oxa = xa - kx;
-    const int oyb = yb - ky, oxb = xb - kx;
     const bool oka = oya >= 0 && oya < S2 && oxa >= 0 && oxa < S2;
-    const bool okb = oyb >= 0 && oyb < S2 && oxb >= 0 && oxb < S2;
     const int ra = oka ? (oya - y0 + 2) * S2 + oxa : 0;
-    const int rb = okb ? (oyb - y0 + 2) * S2 + oxb : 0;
+    bool okb = false;
+    int rb = 0;
+    if constexpr (MF == 2) {
+      const int oyb = yb - ky, oxb = xb - kx;
+      okb = oyb >= 0 && oyb < S2 && oxb >= 0 && oxb < S2;
+      rb = okb ? (oyb - y0 + 2) * S2 + oxb : 0;
+    }
     const float* wk = wt + kyx * 2048;
 #pragma unroll
     for (int ks = 0; ks < C2 / 4; ++ks) {
       const int co = ks * 4 + lk;
       float av0 = sD[ra][co];
-      float av1 = sD[rb][co];
       av0 = oka ? av0 : 0.f;
-      av1 = okb ? av1 : 0.f;
-      const float wk0 = wk[co * C1 + li];
-      const float wk1 = wk[co * C1 + 16 + li];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0, wk0,
-                                                       acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0, wk1,
-                                                       acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1, wk0,
-                                                       acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1, wk1,
-                                                       acc[1][1], 0, 0, 0);
+      float av1 = 0.f;
+      if constexpr (MF == 2) {
+        av1 = sD[rb][co];
+        av1 = okb ? av1 : 0.f;
+      }
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const float bv = wk[co * C1 + ct * 16 + li];
+        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            av0, bv, acc[0][ct], 0, 0, 0);
+        if constexpr (MF == 2)
+          acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              av1, bv, acc[1][ct], 0, 0, 0);
+      }
     }
   }
 #pragma unroll
-  for (int mf = 0; mf < 2; ++mf)
+  for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int pix = p0 + wv * 32 + mf * 16 + lk * 4 + r;
+        const int pix = p0 + (wv * MF + mf) * 16 + lk * 4 + r;
         if (pix < 676)
           dx1[(long long)pix * C1 + ct * 16 + li] = acc[mf][ct][r];
       }
 }
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_conv2_dgrad_mfma2(CnnArgs a) { conv2_dgrad_body<1>(a); }
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_conv2_dgrad_mfma3(CnnArgs a) { conv2_dgrad_body<2>(a); }
 
 // conv1 wgrad, stage 1: per-(g, b) partials into the dz2 scratch region
 // (reused: dz2 is [G, B, 64] and conv1 has 288+32=320 grad entries, so
@@ -1234,10 +1219,8 @@ void cnn_conv1_wgrad_part(CnnArgs a) {
   if (b >= step_n(a, g)) return;
   const int tid = threadIdx.x;
   __shared__ __attribute__((aligned(16))) float xin[D_IN];
-  const float* xs = a.x + (step_o(a, g) + b) * D_IN;
-  const float* xm = a.x_mask ? a.x_mask + (long long)g * D_IN : nullptr;
-  for (int d = tid; d < D_IN; d += WG)
-    xin[d] = xm ? xs[d] * xm[d] : xs[d];
+  stage_masked_input(xin, a.x + (step_o(a, g) + b) * D_IN,
+                     a.x_mask ? a.x_mask + (long long)g * D_IN : nullptr);
   __syncthreads();
   const float* dx = a.dx1 + ((long long)g * a.B + b) * X1N;  // chans-last
   float* out = a.c1part + ((long long)g * a.B + b) * 320;
@@ -1369,23 +1352,17 @@ extern "C" __global__ void cnn_opt_tick(CnnArgs a) {
 
 struct CnnEvalArgs {
   const float* __restrict__ params;     // [M, P]
-  const int64_t* __restrict__ task_row; // [W]
-  const int64_t* __restrict__ task_id;  // [W]
-  const int64_t* __restrict__ off;      // [W]
-  const int64_t* __restrict__ len;      // [W]
-  const int64_t* __restrict__ slot;     // [W] prefix base into a2e
   const float* __restrict__ x;
-  const int64_t* __restrict__ y;
   const float* __restrict__ x_mask;     // [W, 784] or [784] or null
   int xm_per_task;
   float* __restrict__ a2e;              // [slots, NF]
   float* __restrict__ z1e;              // [slots, NH] (fc1 output)
-  float* __restrict__ z1pe;             // [slots, KS, NH] fc1 K-split partials
+  float* __restrict__ z1pe;             // [slots, FC1_KS, NH] fc1 partials
   // fc1 GEMM block metadata (slots grouped by model row, <=64 per block)
   const int64_t* __restrict__ blk_row;
   const int64_t* __restrict__ blk_s0;
   const int64_t* __restrict__ blk_len;
-  // per-slot metadata for the head kernel
+  // per-slot metadata
   const int64_t* __restrict__ srow;     // model row per slot
   const int64_t* __restrict__ stid;     // task id per slot
   const int64_t* __restrict__ sy;       // label per slot
@@ -1406,290 +1383,63 @@ struct CnnEvalArgs {
   int O, P, mode;
 };
 
-// eval conv1: block per slot; the masked input stages in LDS once and
-// each thread produces channels-last x1 elements (9 fused MACs each)
+// eval conv1, block per slot -> x1e [slots, 676, 32]
 extern "C" __global__ __launch_bounds__(WG)
 void cnn_eval_conv1(CnnEvalArgs a) {
   const long long slot = blockIdx.x;
   if (slot >= a.n_slots) return;
-  const int tid = threadIdx.x;
-  __shared__ __attribute__((aligned(16))) float xin[D_IN];
-  __shared__ __attribute__((aligned(16))) float wc[288 + C1];
-  const float* wp = a.params + a.srow[slot] * (long long)a.P;
-  const float* xs = a.x + a.soff[slot] * D_IN;
-  const float* xm = a.x_mask
-      ? a.x_mask + (a.xm_per_task ? a.swin[slot] * D_IN : 0) : nullptr;
-  for (int d = tid; d < D_IN; d += WG)
-    xin[d] = xm ? xs[d] * xm[d] : xs[d];
-  for (int i = tid; i < 288 + C1; i += WG) wc[i] = wp[OFF_W1C + i];
-  __syncthreads();
-  float* out = a.x1e + slot * X1N;
-  for (int e = tid; e < X1N; e += WG) {
-    const int pp = e / C1;
-    const int c = e - pp * C1;
-    const int oy = pp / S1, ox = pp - (pp / S1) * S1;
-    float z = wc[288 + c];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx)
-        z = fmaf(xin[(oy + ky) * IN_W + ox + kx],
-                 wc[c * 9 + ky * 3 + kx], z);
-    out[e] = z;
-  }
+  conv1_fwd_body(
+      a.x + a.soff[slot] * D_IN,
+      a.x_mask ? a.x_mask + (a.xm_per_task ? a.swin[slot] * D_IN : 0)
+               : nullptr,
+      a.params + a.srow[slot] * (long long)a.P, a.x1e + slot * X1N);
 }
 
-// eval conv2 as the region-staged MFMA GEMM (same structure as the
-// train kernel, indexed by slot with per-slot model rows)
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_eval_conv2_mfma(CnnEvalArgs a) {
-  const int pt = blockIdx.x % 9;
-  const long long slot = blockIdx.x / 9;
+// eval conv2, block per (slot, ptile), per-slot model rows; 64-pixel
+// tiles by default, 128-pixel under FEDDRIFT_CONV2FWD=2
+template <int MF>
+__device__ __forceinline__ void conv2_fwd_eval(const CnnEvalArgs& a) {
+  constexpr int TILES = MF == 1 ? 9 : 5;
+  const int pt = blockIdx.x % TILES;
+  const long long slot = blockIdx.x / TILES;
   if (slot >= a.n_slots) return;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const int l = tid & 63;
-  const int li = l & 15, lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sR[6 * S1][C1 + 1];
-  const int p0 = pt * 64;
-  const int r0 = p0 / S2;
-  const float* x1 = a.x1e + slot * X1N + (long long)r0 * S1 * C1;
-  {
-    const int nrow = min(6 * S1, (S1 - r0) * S1);
-    const int r8 = tid >> 5, kk = tid & 31;
-    for (int rr = r8; rr < 6 * S1; rr += 8)
-      sR[rr][kk] = (rr < nrow) ? x1[(long long)rr * C1 + kk] : 0.f;
-  }
-  __syncthreads();
-  f32x4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-  const int p = p0 + wv * 16 + li;
-  const int arow = (p / S2 - r0) * S1 + (p - (p / S2) * S2);
   const long long row = a.srow[slot];
-  const float* wt = a.wtf_e + row * (9 * 2048);
-  for (int kyx = 0; kyx < 9; ++kyx) {
-    const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
-    const int off = arow + ky * S1 + kx;
-    const float* wk = wt + kyx * 2048;
-#pragma unroll
-    for (int ks = 0; ks < C1 / 4; ++ks) {
-      const float av = sR[off][ks * 4 + lk];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            av, wk[(ks * 4 + lk) * C2 + ct * 16 + li], acc[ct], 0, 0, 0);
-    }
-  }
-  const float* bias = a.params + row * (long long)a.P + OFF_B2C;
-  float* z2 = a.z2e + slot * Z2N;
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int co = ct * 16 + li;
-    const float bb = bias[co];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int pp = p0 + wv * 16 + lk * 4 + r;
-      z2[(long long)pp * C2 + co] = acc[ct][r] + bb;
-    }
-  }
+  conv2_fwd_body<MF>(a.x1e + slot * X1N, a.wtf_e + row * (9 * 2048),
+                     a.params + row * (long long)a.P + OFF_B2C,
+                     a.z2e + slot * Z2N, pt);
 }
-
-// eval conv2, 128-pixel tiles (see cnn_conv2_fwd_mfma2)
 extern "C" __global__ __launch_bounds__(WG)
-void cnn_eval_conv2_mfma2(CnnEvalArgs a) {
-  const int pt = blockIdx.x % 5;
-  const long long slot = blockIdx.x / 5;
-  if (slot >= a.n_slots) return;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const int l = tid & 63;
-  const int li = l & 15, lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sR[8 * S1][C1 + 1];
-  const int p0 = pt * 128;
-  const int r0 = p0 / S2;
-  const float* x1 = a.x1e + slot * X1N + (long long)r0 * S1 * C1;
-  {
-    const int nrow = min(8 * S1, (S1 - r0) * S1);
-    const int r8 = tid >> 5, kk = tid & 31;
-    for (int rr = r8; rr < 8 * S1; rr += 8)
-      sR[rr][kk] = (rr < nrow) ? x1[(long long)rr * C1 + kk] : 0.f;
-  }
-  __syncthreads();
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[mf][t] = {0.f, 0.f, 0.f, 0.f};
-  const int p_a = p0 + wv * 32 + li;
-  const int p_b = p_a + 16;
-  const int arow_a = (p_a / S2 - r0) * S1 + (p_a - (p_a / S2) * S2);
-  const int arow_b = (p_b / S2 - r0) * S1 + (p_b - (p_b / S2) * S2);
-  const long long row = a.srow[slot];
-  const float* wt = a.wtf_e + row * (9 * 2048);
-  for (int kyx = 0; kyx < 9; ++kyx) {
-    const int ky = kyx / 3, kx = kyx - (kyx / 3) * 3;
-    const int offa = arow_a + ky * S1 + kx;
-    const int offb = arow_b + ky * S1 + kx;
-    const float* wk = wt + kyx * 2048;
-#pragma unroll
-    for (int ks = 0; ks < C1 / 4; ++ks) {
-      const float av0 = sR[offa][ks * 4 + lk];
-      const float av1 = sR[offb][ks * 4 + lk];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const float wv_ = wk[(ks * 4 + lk) * C2 + ct * 16 + li];
-        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0, wv_,
-                                                          acc[0][ct],
-                                                          0, 0, 0);
-        acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1, wv_,
-                                                          acc[1][ct],
-                                                          0, 0, 0);
-      }
-    }
-  }
-  const float* bias = a.params + row * (long long)a.P + OFF_B2C;
-  float* z2 = a.z2e + slot * Z2N;
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int co = ct * 16 + li;
-    const float bb = bias[co];
-#pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int pp = p0 + wv * 32 + mf * 16 + lk * 4 + r;
-        if (pp < Z2N / C2)
-          z2[(long long)pp * C2 + co] = acc[mf][ct][r] + bb;
-      }
-  }
-}
+void cnn_eval_conv2_mfma(CnnEvalArgs a) { conv2_fwd_eval<1>(a); }
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_eval_conv2_mfma2(CnnEvalArgs a) { conv2_fwd_eval<2>(a); }
 
-// eval maxpool, block per slot: channels-last z2 reads coalesced via
-// LDS row staging, pooled a2e assembled in LDS and stored in one
-// coalesced pass (torch-flatten layout; no dropout, no argmax at eval)
+// eval maxpool, block per slot: pooled a2e assembled in LDS and stored
+// in one coalesced pass (torch-flatten layout; no dropout, no argmax)
 extern "C" __global__ __launch_bounds__(WG)
 void cnn_eval_pool(CnnEvalArgs a) {
   const long long slot = blockIdx.x;
   if (slot >= a.n_slots) return;
-  const int tid = threadIdx.x;
-  __shared__ __attribute__((aligned(16))) float srow_[2][2 * S2 * C2];
   __shared__ __attribute__((aligned(16))) float sa2[NF];
-  const float* z2 = a.z2e + slot * Z2N;
-  // double-buffered row-pair staging (same pattern as cnn_pool_fwd):
-  // the next pooled row's z2 loads issue before this row's max pass
-  float rst[12];
-#define PE_LOAD(py)                                                     \
-  _Pragma("unroll") for (int jj = 0; jj < 12; ++jj)                      \
-    rst[jj] = z2[(long long)(2 * (py)) * S2 * C2 + tid + jj * WG];
-#define PE_WRITE(buf)                                                   \
-  _Pragma("unroll") for (int jj = 0; jj < 12; ++jj)                      \
-    srow_[buf][tid + jj * WG] = rst[jj];
-  PE_LOAD(0);
-  PE_WRITE(0);
-  __syncthreads();
-  int cur = 0;
-  for (int py = 0; py < SP; ++py) {
-    if (py + 1 < SP) { PE_LOAD(py + 1); }
-    for (int q = tid; q < C2 * SP; q += WG) {
-      const int c = q / SP;
-      const int px = q - c * SP;
-      float best = -1e30f;
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx)
-          best = fmaxf(best, srow_[cur][(dy * S2 + 2 * px + dx) * C2 + c]);
-      sa2[c * (SP * SP) + py * SP + px] = best;
-    }
-    if (py + 1 < SP) { PE_WRITE(cur ^ 1); }
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef PE_LOAD
-#undef PE_WRITE
+  pool_rows_body<false>(a.z2e + slot * Z2N, sa2, nullptr);
   float* out = a.a2e + slot * (long long)NF;
-  for (int e = tid; e < NF; e += WG) out[e] = sa2[e];
+  for (int e = threadIdx.x; e < NF; e += WG) out[e] = sa2[e];
 }
 
-// fc1 eval as an MFMA tile GEMM with the SAME K-split as the training
-// fc1 (the eval grid is otherwise tiny: ~4000 slots = 63 blocks for
-// 256 CUs — per-wave PMC showed healthy 37% MFMA busy but only a
-// quarter of the chip occupied): block (blk, ks) computes the partial
-// z1 for up to 64 consecutive same-row slots x 128 h over K-range
-// [ks*NF/KS, ...), partials land in z1pe and cnn_eval_fc1_act folds
-// them with bias + relu. 4 waves x 16 rows x 128 cols, f32-input MFMA,
-// BK=32 double-buffered register-staged LDS tiles with +1 padding.
-#define EVAL_FC1_KS 8
+// eval fc1 with the training K-split (the eval grid is otherwise tiny:
+// ~4000 slots = 63 blocks for 256 CUs — per-wave PMC showed healthy 37%
+// MFMA busy but only a quarter of the chip occupied): block (blk, ks)
+// computes the partial z1 for up to 64 consecutive same-row slots;
+// partials land in z1pe [slots, FC1_KS, NH]
 extern "C" __global__ __launch_bounds__(WG)
 void cnn_eval_fc1_mfma(CnnEvalArgs a) {
-  const int ks = blockIdx.x % EVAL_FC1_KS;
-  const int blk = blockIdx.x / EVAL_FC1_KS;
-  const long long row = a.blk_row[blk];
+  const int ks = blockIdx.x % FC1_KS;
+  const int blk = blockIdx.x / FC1_KS;
   const long long s0 = a.blk_s0[blk];
-  const int mlen = (int)a.blk_len[blk];
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const int l = tid & 63;
-  const int li = l & 15;
-  const int lk = l >> 4;
-  __shared__ __attribute__((aligned(16))) float sA[2][64][EVAL_BK + 1];
-  __shared__ __attribute__((aligned(16))) float sB[2][EVAL_BK][NH + 1];
-  f32x4 acc[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-  const float* wp = a.params + row * (long long)a.P + OFF_W1F;
-  const int r8 = tid >> 5, kk = tid & 31;
-  const int k_lo = ks * (NF / EVAL_FC1_KS);
-  const int k_hi = (ks + 1) * (NF / EVAL_FC1_KS);
-  // register staging: 8 A rows + 16 B rows per thread per tile
-  float ra[8], rb[16];
-#define EV_LOAD(k0)                                                     \
-  _Pragma("unroll") for (int j = 0; j < 8; ++j) {                        \
-    const int rr = r8 + j * 8;                                           \
-    ra[j] = (rr < mlen) ? a.a2e[(s0 + rr) * (long long)NF + (k0) + kk]   \
-                        : 0.f;                                           \
-  }                                                                      \
-  _Pragma("unroll") for (int j = 0; j < 16; ++j)                         \
-    rb[j] = wp[(long long)(r8 + j * 8) * NF + (k0) + kk];
-#define EV_WRITE(buf)                                                   \
-  _Pragma("unroll") for (int j = 0; j < 8; ++j)                          \
-    sA[buf][r8 + j * 8][kk] = ra[j];                                     \
-  _Pragma("unroll") for (int j = 0; j < 16; ++j)                         \
-    sB[buf][kk][r8 + j * 8] = rb[j];
-  EV_LOAD(k_lo);
-  EV_WRITE(0);
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = k_lo; k0 < k_hi; k0 += EVAL_BK) {
-    if (k0 + EVAL_BK < k_hi) { EV_LOAD(k0 + EVAL_BK); }
-#pragma unroll
-    for (int kq = 0; kq < EVAL_BK / 4; ++kq) {
-      const float av = sA[cur][wv * 16 + li][kq * 4 + lk];
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            av, sB[cur][kq * 4 + lk][ct * 16 + li], acc[ct], 0, 0, 0);
-    }
-    if (k0 + EVAL_BK < k_hi) { EV_WRITE(cur ^ 1); }
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef EV_LOAD
-#undef EV_WRITE
-  // epilogue: partials out (bias + relu fold in cnn_eval_fc1_act)
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int mrow = wv * 16 + lk * 4 + r;
-      if (mrow < mlen) {
-        const int h = ct * 16 + li;
-        a.z1pe[((s0 + mrow) * EVAL_FC1_KS + ks) * (long long)NH + h] =
-            acc[ct][r];
-      }
-    }
-  }
+  fc1_tile_body(a.a2e + s0 * (long long)NF, (int)a.blk_len[blk],
+                a.params + a.blk_row[blk] * (long long)a.P + OFF_W1F,
+                ks * (NF / FC1_KS), (ks + 1) * (NF / FC1_KS),
+                a.z1pe + (s0 * FC1_KS + ks) * (long long)NH,
+                (long long)FC1_KS * NH);
 }
 
 // fold the eval fc1 K-split partials + bias, apply relu -> z1e
@@ -1700,41 +1450,27 @@ void cnn_eval_fc1_act(CnnEvalArgs a) {
        q += (long long)gridDim.x * WG) {
     const long long slot = q / NH;
     const int h = (int)(q - slot * NH);
-    const float* wp = a.params + a.srow[slot] * (long long)a.P;
-    float z = wp[OFF_B1F + h];
-#pragma unroll
-    for (int ks = 0; ks < EVAL_FC1_KS; ++ks)
-      z += a.z1pe[(slot * EVAL_FC1_KS + ks) * (long long)NH + h];
+    const float z = fc1_fold(
+        a.params[a.srow[slot] * (long long)a.P + OFF_B1F + h],
+        a.z1pe + slot * FC1_KS * (long long)NH + h, NH);
     a.z1e[q] = z > 0.f ? z : 0.f;
   }
 }
 
-// head: per-slot fc2 + in-graph softmax + mode tail. ONE WAVE per slot
-// (same shape as cnn_head_fwd): lane o owns output o, the z1 row loads
-// once into two coalesced registers, softmax/argmax run as shuffle
-// reductions, atomic tails issue from lane 0.
+// head: per-slot fc2 + in-graph softmax (head_softmax, ONE WAVE per
+// slot) + mode tail: argmax runs as a shuffle reduction, atomic tails
+// issue from lane 0.
 extern "C" __global__ __launch_bounds__(WG)
 void cnn_eval_head(CnnEvalArgs a) {
   const int l = threadIdx.x & 63;
   for (long long slot = (long long)blockIdx.x * (WG / 64)
                         + (threadIdx.x >> 6);
        slot < a.n_slots; slot += (long long)gridDim.x * (WG / 64)) {
-    const long long row = a.srow[slot];
-    const float* wp = a.params + row * (long long)a.P;
-    const float* z1 = a.z1e + slot * NH;
-    const float r0 = z1[l], r1 = z1[64 + l];
-    float zlane = 0.f;
-    for (int o = 0; o < a.O; ++o) {
-      const float* wo = wp + OFF_W2F + (long long)o * NH;
-      const float v = wave_sum(fmaf(r0, wo[l], r1 * wo[64 + l]));
-      if (l == o) zlane = v;
-    }
     const bool live = l < a.O;
-    float z = live ? zlane + wp[OFF_W2F + (long long)a.O * NH + l]
-                   : -1e30f;
-    const float zmax = wave_max(z);
-    float e = live ? __expf(z - zmax) : 0.f;
-    const float s = e / wave_sum(e);   // the model OUTPUT (in-graph softmax)
+    // the model OUTPUT (in-graph softmax)
+    const float s = head_softmax(a.z1e + slot * NH,
+                                 a.params + a.srow[slot] * (long long)a.P,
+                                 a.O, l);
     // argmax, LOWEST index on ties (the sequential scan used strict >)
     float bv = live ? s : -1e30f;
     int bi = live ? l : 64;
@@ -1789,6 +1525,15 @@ static int grid_for(long long total) {
   if (b > 16384) b = 16384;          // grid-stride beyond
   return (int)(b < 1 ? 1 : b);
 }
+
+// Launch macros of the two host functions below. They capture two
+// locals of the function they are used in: `s`, the current HIP stream,
+// and `a`, its kernel-argument struct (CnnArgs in cnn_train_epoch_impl,
+// CnnEvalArgs in cnn_eval). LB takes an explicit block count, L sizes a
+// grid-stride grid from a thread total; both launch WG threads per block.
+#define LB(kern, blocks) \
+  hipLaunchKernelGGL(kern, dim3((int)(blocks)), dim3(WG), 0, s, a)
+#define L(kern, total) LB(kern, grid_for(total))
 
 void cnn_train_epoch_impl(
     torch::Tensor work, torch::Tensor grad, torch::Tensor rows,
@@ -1854,34 +1599,26 @@ void cnn_train_epoch_impl(
 
   auto s = c10::hip::getCurrentHIPStream();
   const long long GB = (long long)G * B;
-#define L(kern, total) \
-  hipLaunchKernelGGL(kern, dim3(grid_for(total)), dim3(WG), 0, s, a)
   const int mtiles = (a.B + 63) / 64;
   // forward
   L(cnn_w2_reshape, (long long)G * C2 * C1 * 9);
-  hipLaunchKernelGGL(cnn_conv1_fwd, dim3((int)GB), dim3(WG), 0, s, a);
+  LB(cnn_conv1_fwd, GB);
   if (fwd_v2())
-    hipLaunchKernelGGL(cnn_conv2_fwd_mfma2, dim3((int)GB * 5), dim3(WG), 0,
-                       s, a);
+    LB(cnn_conv2_fwd_mfma2, GB * 5);
   else
-    hipLaunchKernelGGL(cnn_conv2_fwd_mfma, dim3((int)GB * 9), dim3(WG), 0,
-                       s, a);
-  hipLaunchKernelGGL(cnn_pool_fwd, dim3((int)GB), dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_fc1_fwd_mfma, dim3(G * mtiles * FC1_KS), dim3(WG),
-                     0, s, a);
+    LB(cnn_conv2_fwd_mfma, GB * 9);
+  LB(cnn_pool_fwd, GB);
+  LB(cnn_fc1_fwd_mfma, G * mtiles * FC1_KS);
   L(cnn_fc1_act, GB * NH);
   L(cnn_head_fwd, GB * 64);   // one wave per sample
   // backward
   L(cnn_fc2_wgrad, (long long)G * O * NH);
   L(cnn_fc2_dgrad, GB * NH);
-  hipLaunchKernelGGL(cnn_fc1_wgrad, dim3(G * (NF / 128)), dim3(WG), 0, s,
-                     a);
+  LB(cnn_fc1_wgrad, G * (NF / 128));
   L(cnn_fc1_bias_grad, (long long)G * NH);
-  hipLaunchKernelGGL(cnn_fc1_dgrad, dim3(G * mtiles * (NF / 128)),
-                     dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_pool_bwd, dim3((int)GB), dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_conv2_wgrad_mfma, dim3(G * a.w2ms), dim3(WG),
-                     0, s, a);
+  LB(cnn_fc1_dgrad, G * mtiles * (NF / 128));
+  LB(cnn_pool_bwd, GB);
+  LB(cnn_conv2_wgrad_mfma, G * a.w2ms);
   L(cnn_conv2_wgrad_reduce, (long long)G * (9 * 2048 + C2));
   // dgrad variant switch, A/B-measured at both ends of the fleet-size
   // axis (FEDDRIFT_DGRAD=1|2|3 forces one): v3 (128-pixel tiles, every
@@ -1898,35 +1635,27 @@ void cnn_train_epoch_impl(
     hipLaunchKernelGGL(cnn_conv2_dgrad_mfma, dim3((int)GB), dim3(WG),
                        (9 * 2048 + 2 * DG_RC * 64) * sizeof(float), s, a);
   else if (dgrad_v == 3)
-    hipLaunchKernelGGL(cnn_conv2_dgrad_mfma3, dim3((int)GB * 6), dim3(WG),
-                       0, s, a);
+    LB(cnn_conv2_dgrad_mfma3, GB * 6);
   else
-    hipLaunchKernelGGL(cnn_conv2_dgrad_mfma2, dim3((int)GB * 11), dim3(WG),
-                       0, s, a);
-  hipLaunchKernelGGL(cnn_conv1_wgrad_part, dim3(G * (int)B), dim3(WG), 0,
-                     s, a);
+    LB(cnn_conv2_dgrad_mfma2, GB * 11);
+  LB(cnn_conv1_wgrad_part, GB);
   L(cnn_conv1_wgrad_reduce, (long long)G * 320);
   // optimizer
   L(cnn_opt_step, (long long)G * a.P);
-  hipLaunchKernelGGL(cnn_opt_tick, dim3((G + WG - 1) / WG), dim3(WG), 0, s,
-                     a);
-#undef L
+  LB(cnn_opt_tick, (G + WG - 1) / WG);
   TORCH_CHECK(hipGetLastError() == hipSuccess, "cnn_train_epoch launch");
 }
 
 torch::Tensor cnn_eval(
-    torch::Tensor params, torch::Tensor task_row, torch::Tensor task_id,
-    torch::Tensor off, torch::Tensor len, torch::Tensor slot,
-    torch::Tensor x, torch::Tensor y, torch::Tensor a2e, torch::Tensor z1e,
-    torch::Tensor z1pe,
+    torch::Tensor params, torch::Tensor x, torch::Tensor a2e,
+    torch::Tensor z1e, torch::Tensor z1pe,
     torch::Tensor x1e, torch::Tensor z2e, torch::Tensor wtf_e,
     torch::Tensor blk_row, torch::Tensor blk_s0, torch::Tensor blk_len,
     torch::Tensor srow, torch::Tensor stid, torch::Tensor sy,
     torch::Tensor soff, torch::Tensor swin,
     c10::optional<torch::Tensor> x_mask, int64_t n_tasks, int64_t O,
-    int64_t mode, bool want_mse, int64_t max_len, int64_t n_slots,
+    int64_t mode, bool want_mse, int64_t n_slots,
     c10::optional<torch::Tensor> outp) {
-  const int W = task_row.size(0);
   auto optd = torch::TensorOptions().dtype(torch::kFloat64)
                   .device(params.device());
   torch::Tensor out;
@@ -1936,17 +1665,11 @@ torch::Tensor cnn_eval(
     out = torch::zeros({n_tasks, O, O}, optd);
   else
     out = torch::zeros({0}, optd);
-  if (W == 0 || n_slots == 0) return out;
+  if (n_slots == 0) return out;
 
   CnnEvalArgs a;
   a.params = params.data_ptr<float>();
-  a.task_row = task_row.data_ptr<int64_t>();
-  a.task_id = task_id.data_ptr<int64_t>();
-  a.off = off.data_ptr<int64_t>();
-  a.len = len.data_ptr<int64_t>();
-  a.slot = slot.data_ptr<int64_t>();
   a.x = x.data_ptr<float>();
-  a.y = y.data_ptr<int64_t>();
   a.x_mask = x_mask.has_value() ? x_mask->data_ptr<float>() : nullptr;
   a.xm_per_task = x_mask.has_value() && x_mask->dim() == 2 ? 1 : 0;
   a.a2e = a2e.data_ptr<float>();
@@ -1976,29 +1699,33 @@ torch::Tensor cnn_eval(
   a.mode = (int)mode;
 
   auto s = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(cnn_eval_conv1, dim3((int)n_slots), dim3(WG), 0, s,
-                     a);
+  LB(cnn_eval_conv1, n_slots);
   if (fwd_v2())
-    hipLaunchKernelGGL(cnn_eval_conv2_mfma2, dim3((int)(n_slots * 5)),
-                       dim3(WG), 0, s, a);
+    LB(cnn_eval_conv2_mfma2, n_slots * 5);
   else
-    hipLaunchKernelGGL(cnn_eval_conv2_mfma, dim3((int)(n_slots * 9)),
-                       dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_eval_pool, dim3((int)n_slots), dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_eval_fc1_mfma,
-                     dim3((int)blk_row.size(0) * EVAL_FC1_KS),
-                     dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_eval_fc1_act, dim3(grid_for(n_slots * NH)),
-                     dim3(WG), 0, s, a);
-  hipLaunchKernelGGL(cnn_eval_head, dim3(grid_for(n_slots * 64)), dim3(WG), 0,
-                     s, a);
+    LB(cnn_eval_conv2_mfma, n_slots * 9);
+  LB(cnn_eval_pool, n_slots);
+  LB(cnn_eval_fc1_mfma, blk_row.size(0) * FC1_KS);
+  L(cnn_eval_fc1_act, n_slots * NH);
+  L(cnn_eval_head, n_slots * 64);   // one wave per slot
   TORCH_CHECK(hipGetLastError() == hipSuccess, "cnn_eval launch");
-  (void)max_len;
   return out;
 }
+#undef L
+#undef LB
 
 void register_cnn(pybind11::module_& mod) {
   mod.def("cnn_train_epoch", &cnn_train_epoch_impl,
           "one fused CNN training epoch over all (client, model) pairs");
   mod.def("cnn_eval", &cnn_eval, "batched CNN eval sweep (acc/conf/dump)");
+  // geometry and mode constants the Python engine sizes its buffers by
+  mod.attr("X1N") = X1N;
+  mod.attr("Z2N") = Z2N;
+  mod.attr("NF") = NF;
+  mod.attr("NH") = NH;
+  mod.attr("D_IN") = D_IN;
+  mod.attr("FC1_KS") = FC1_KS;
+  mod.attr("EV_ACC") = EV_ACC;
+  mod.attr("EV_CONF") = EV_CONF;
+  mod.attr("EV_DUMP") = EV_DUMP;
 }
