@@ -66,6 +66,10 @@ class Config:
     # robust aggregation (fedavg_robust / fedml_core robustness equivalent)
     secure_agg: int = 0                  # 1: pairwise-mask uploads
                                          # (turboaggregate equivalent)
+                                         # 2: exact ring-arithmetic masks
+    secure_agg_degree: int = 0           # mode 2 mask graph: 0 = complete,
+                                         # d (even) = d neighbours per worker
+    secure_agg_frac_bits: int = 24       # mode 2 fixed-point fraction bits
     robust_norm_bound: float = 0.0       # >0: clip client updates to this L2
     robust_noise: float = 0.0            # >0: Gaussian noise stddev on avg
     # FedOpt server optimizer ('avg' = plain FedAvg replacement)
@@ -74,6 +78,12 @@ class Config:
 
     def __post_init__(self):
         self.dataset_norm = "MNIST" if self.dataset.lower() == "mnist" else self.dataset
+        if self.secure_agg_degree < 0 or self.secure_agg_degree % 2:
+            raise ValueError("secure_agg_degree must be even and >= 0, got "
+                             f"{self.secure_agg_degree}")
+        if not 0 <= self.secure_agg_frac_bits <= 40:
+            raise ValueError("secure_agg_frac_bits must lie in [0, 40], got "
+                             f"{self.secure_agg_frac_bits}")
 
     @property
     def is_softcluster(self) -> bool:

@@ -287,6 +287,21 @@ class FLJob:
         self._eval_fast: Optional[tuple] = None
         self._partial: Optional[torch.Tensor] = None
         self._partial_fused = False
+        # secure_agg=2 (ring arithmetic): intra-rank pairs cancel inside a
+        # rank's contribution, so they are skipped unless this switch is
+        # cleared (a world-1 run then draws every mask; tests and the
+        # secure-aggregation benchmark use it)
+        self.secagg_skip_intra = True
+        self.secagg_keep_contrib = False   # keep the pre-reduce tensor
+        self._secagg_contrib: Optional[torch.Tensor] = None
+        self._secagg_flag: Optional[torch.Tensor] = None
+        self._secagg_plans: Dict = {}
+        self._secure_ctr = 0
+        if cfg.secure_agg == 2:
+            from ..comm import secure_agg as _sa
+            assert comm.world_size <= _sa.MAX_WORLD, \
+                f"secure_agg=2 supports at most {_sa.MAX_WORLD} ranks"
+            self._secagg_base = _sa.job_key(cfg.dummy_arg, self.curr_iter)
         self.algo.init_iteration(self)
 
     # ------------------------------------------------------------------
@@ -452,18 +467,21 @@ class FLJob:
         robust = self.cfg.robust_norm_bound > 0
         hip = (not self.is_module_path) and self.backend is not ops.mlp_torch \
             and not robust   # clipping happens between train and aggregate
+        # ring-arithmetic secure aggregation reads the replicas itself: the
+        # launch keeps its fused broadcast but drops the float partial
+        ring = self.cfg.secure_agg == 2
         if self._partial is None or self._partial.shape[0] != K:
             self._partial = torch.zeros(K, P + 1, device=dev)
             self._totals = torch.zeros(K, device=dev)
             self._partial_clean = True
-        if hip:
+        if hip and not ring:
             # the apply kernel drains partial to zero on its way out, so
             # steady-state rounds skip this fill entirely
             if not getattr(self, "_partial_clean", False):
                 self._partial.zero_()
             self._partial_clean = False
         if plan.rows.size == 0:
-            self._partial_fused = hip
+            self._partial_fused = hip and not ring
             if not hip and not self.is_module_path:
                 self.sync_replicas()
             return
@@ -495,9 +513,9 @@ class FLJob:
                 self.spec, self.replicas, rows_t, self.arena.x, self.arena.y,
                 off_t, len_t, self.opt, x_mask=plan.x_mask,
                 in_params=self.global_params,
-                model_of=mo_t, sample_w=sw_t,
-                partial=self._partial)
-            self._partial_fused = True
+                model_of=mo_t, sample_w=None if ring else sw_t,
+                partial=None if ring else self._partial)
+            self._partial_fused = not ring
         else:
             self.sync_replicas()
             rows_t = torch.as_tensor(plan.rows, dtype=torch.int64, device=dev)
@@ -559,21 +577,28 @@ class FLJob:
         left untouched), matching the softcluster skip rule
         (FedAvgEnsAggregatorSoftCluster.py:151-153). Returns total weights
         per model (device tensor). Models with zero total weight are
-        skipped (:167-169)."""
+        skipped (:167-169).
+
+        secure_agg=2 replaces the float partial + all_reduce with the
+        ring-arithmetic path (_secure_ring_partial); everything after the
+        all_reduce is shared."""
         K, P = self.n_models, self.n_params
         partial = self._partial
-        if not self._partial_fused:
-            nW = len(self.owned_workers)
-            partial.zero_()
-            if nW:
-                w = torch.as_tensor(plan.sample_num, dtype=torch.float32,
-                                    device=self.device)      # [nW, K]
-                reps = self.replicas.reshape(nW, K, P)
-                partial[:, :P] = torch.einsum("wk,wkp->kp", w, reps)
-                partial[:, P] = w.sum(dim=0)
-        if self.cfg.secure_agg:
-            self._apply_secure_masks(plan, partial)
-        self.comm.all_reduce_(partial)
+        if self.cfg.secure_agg == 2:
+            self._secure_ring_partial(plan, partial)
+        else:
+            if not self._partial_fused:
+                nW = len(self.owned_workers)
+                partial.zero_()
+                if nW:
+                    w = torch.as_tensor(plan.sample_num, dtype=torch.float32,
+                                        device=self.device)      # [nW, K]
+                    reps = self.replicas.reshape(nW, K, P)
+                    partial[:, :P] = torch.einsum("wk,wkp->kp", w, reps)
+                    partial[:, P] = w.sum(dim=0)
+            if self.cfg.secure_agg:
+                self._apply_secure_masks(plan, partial)
+            self.comm.all_reduce_(partial)
         totals = partial[:, P]
         mask_t = None
         if model_mask is not None:
@@ -637,7 +662,7 @@ class FLJob:
                     act[w, m] = 1.0
         self.comm.all_reduce_(act)
         act_np = act.cpu().numpy() > 0
-        self._secure_ctr = getattr(self, "_secure_ctr", 0) + 1
+        self._secure_ctr += 1
         base = (self.cfg.dummy_arg * 1009 + self.curr_iter) * 65537 \
             + self._secure_ctr
         owned = set(self.owned_workers)
@@ -650,6 +675,75 @@ class FLJob:
                     partial[m, :P] += mask_for(
                         int(w), [int(o) for o in ws], P, base * K + m,
                         self.device)
+
+    def _secagg_plan(self, plan: TrainPlan):
+        """The cached upload/graph structure of this plan. The active
+        (worker, model) set is agreed with one small all_reduce; at world 1
+        this rank knows it already, so an unchanged plan template skips
+        the host work entirely."""
+        from ..comm.secure_agg import build_mask_graph
+        from ..ops.secagg_hip import SecaggPlan
+        K, W = self.n_models, self.n_workers
+        tmpl = plan.template
+        local = not self.comm.distributed
+        if local and tmpl is not None:
+            hit = getattr(tmpl, "_secagg", None)
+            if hit is not None and hit[0] is plan.sample_num:
+                return hit[1]
+        own = np.asarray(self.owned_workers, dtype=np.int64)
+        sn = np.asarray(plan.sample_num).reshape(len(own), K)
+        act = np.zeros((W, K), dtype=bool)
+        act[own] = sn > 0
+        if not local:
+            act_t = torch.as_tensor(act.astype(np.float32),
+                                    device=self.device)
+            self.comm.all_reduce_(act_t)
+            act = act_t.cpu().numpy() > 0
+        key = (act.tobytes(), sn.tobytes())
+        sp = self._secagg_plans.get(key)
+        if sp is None:
+            graph = build_mask_graph(act, self.cfg.secure_agg_degree,
+                                     self.cfg.dummy_arg, self.curr_iter)
+            wi, mo = np.nonzero(sn > 0)
+            sp = SecaggPlan(wi * K + mo, own[wi], mo, sn[wi, mo], K, graph)
+            if len(self._secagg_plans) >= 16:
+                self._secagg_plans.clear()
+            self._secagg_plans[key] = sp
+        if local and tmpl is not None:
+            tmpl._secagg = (plan.sample_num, sp)
+        return sp
+
+    def _secure_ring_partial(self, plan: TrainPlan,
+                             partial: torch.Tensor) -> None:
+        """secure_agg=2: quantise + mask the owned uploads in the ring
+        Z_{2^56} (one launch), all_reduce the int64 tensor, dequantise into
+        `partial`. Masks cancel exactly, whatever the summation order."""
+        from ..ops import secagg_hip
+        F = self.cfg.secure_agg_frac_bits
+        sp = self._secagg_plan(plan)
+        self._secure_ctr += 1
+        if self._secagg_flag is None:
+            self._secagg_flag = secagg_hip.new_flag(self.device)
+        ring, _ = secagg_hip.contribution(
+            self.replicas, sp, self._secagg_base, self._secure_ctr, F,
+            self.n_workers, self.comm.rank, self.comm.world_size,
+            skip_intra=self.secagg_skip_intra, flag=self._secagg_flag)
+        if self.secagg_keep_contrib:
+            self._secagg_contrib = ring.clone()
+        self.comm.all_reduce_(ring)
+        secagg_hip.dequantise(ring, partial, F)
+        self._partial_clean = False
+        if self.device.type != "cuda":
+            self.check_secure_guard()    # no sync to save on the host
+
+    def check_secure_guard(self) -> None:
+        """Raise if a secure_agg=2 upload left the ring's range (the flag
+        is sticky; on a GPU this synchronises, so it is called where the
+        round loop synchronises anyway)."""
+        if self._secagg_flag is not None:
+            from ..ops import secagg_hip
+            secagg_hip.check_flag(self._secagg_flag,
+                                  self.cfg.secure_agg_frac_bits)
 
     def client_sampling(self, round_idx: int) -> np.ndarray:
         """Reference client_sampling (FedAvgEnsAggregatorSoftCluster.py:197-204):
@@ -897,6 +991,7 @@ class FLJob:
                 self.algo.post_aggregate(self, r)
             with timer.phase("test"):
                 self.algo.test(self, r)
+                self.check_secure_guard()
             client_idx = self.client_sampling(r + 1)
         self.save_model_params()
         self.algo.finalize(self)

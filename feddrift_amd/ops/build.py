@@ -13,6 +13,9 @@ import os
 _DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_DIR, "hip", "feddrift_kernels.hip")
 SRC_CNN = os.path.join(_DIR, "hip", "cnn_kernels.hip")
+SRC_SECAGG = os.path.join(_DIR, "hip", "secagg_kernels.hip")
+# the one source list both build functions compile
+SOURCES = [SRC, SRC_CNN, SRC_SECAGG]
 BUILD_DIR = os.path.join(_DIR, "hip", "_build")
 MODULE_NAME = "feddrift_hip"
 
@@ -23,7 +26,7 @@ def build(verbose: bool = False):
     from torch.utils.cpp_extension import load
     mod = load(
         name=MODULE_NAME,
-        sources=[SRC, SRC_CNN],
+        sources=list(SOURCES),
         build_directory=BUILD_DIR,
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
@@ -65,8 +68,8 @@ def build_asan(verbose: bool = False) -> str:
             "-D__HIP_NO_HALF_CONVERSIONS__=1",
             "-DHIP_ENABLE_WARP_SYNC_BUILTINS=1"]
            + [f"-I{i}" for i in incs]
-           + [SRC, SRC_CNN,
-              f"-L{os.path.abspath(torch_lib)}", "-lc10", "-lc10_hip",
+           + list(SOURCES)
+           + [f"-L{os.path.abspath(torch_lib)}", "-lc10", "-lc10_hip",
               "-ltorch_cpu", "-ltorch_hip", "-ltorch", "-ltorch_python",
               "-L/opt/rocm/lib", "-lamdhip64", "-o", out])
     subprocess.run(cmd, check=True,

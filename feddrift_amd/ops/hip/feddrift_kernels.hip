@@ -1093,6 +1093,7 @@ void apply_aggregate_hip(torch::Tensor global_params, torch::Tensor partial,
 }
 
 void register_cnn(pybind11::module_& mod);  // cnn_kernels.hip
+void register_secagg(pybind11::module_& mod);  // secagg_kernels.hip
 
 torch::Tensor ens_vote_multi_hip(
     torch::Tensor params, torch::Tensor weights, torch::Tensor x,
@@ -1176,4 +1177,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("confusion_tasks", &confusion_tasks_hip,
           "batched per-task confusion matrices (KUE)");
   register_cnn(mod);
+  register_secagg(mod);
 }
