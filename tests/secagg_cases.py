@@ -97,6 +97,27 @@ def mean_and_bound(replicas, sample_num, K, frac_bits=F):
     return mean, bound, tot > 0
 
 
+def mean_and_bound_atomic(replicas, sample_num, K):
+    """The sibling of mean_and_bound for the default (float) aggregation:
+    fp32 products n_w theta_w added in fp32 in any order, then one fp32
+    multiply by the reciprocal of the total. Per element
+      2 n_terms 2^-24 sum_w |n_w theta_w| / sum n + 4 2^-24 |mean|,
+    n_terms = the model's count of workers with a positive weight (one
+    rounding of each product, one of each running sum)."""
+    reps = replicas.detach().cpu().double().numpy()
+    nW = sample_num.shape[0]
+    reps = reps.reshape(nW, K, -1)
+    n = np.asarray(sample_num, dtype=np.float32).astype(np.float64)
+    tot = n.sum(axis=0)                                    # [K]
+    safe = np.where(tot > 0, tot, 1.0)
+    mean = np.einsum("wk,wkp->kp", n, reps) / safe[:, None]
+    mag = np.abs(n[:, :, None] * reps).sum(axis=0)
+    n_terms = np.maximum((n > 0).sum(axis=0), 1)           # [K]
+    bound = (2.0 * n_terms * 2.0 ** -24 / safe)[:, None] * mag \
+        + 4.0 * 2.0 ** -24 * np.abs(mean)
+    return mean, bound, tot > 0
+
+
 def make_job(tmp_path, device=None, n_clients=4, k=2, **cfg_kw):
     """The setup of tests/test_secure_agg.py."""
     from feddrift_amd.comm import Communicator

@@ -191,6 +191,9 @@ VARIANTS = [
     ({"FEDDRIFT_DGRAD": "1"}, "cnn_grad_edges"),
     ({"FEDDRIFT_DGRAD": "2"}, "cnn_grad_edges"),
     ({"FEDDRIFT_TRAIN_BS64_MIN_G": "1000000"}, "small_train"),
+    # tests/test_gpu_mlp_rounds.py, parts A and B, on the 256-thread build
+    ({"FEDDRIFT_TRAIN_BS64_MIN_G": "1000000"}, "rounds_small_train"),
+    ({"FEDDRIFT_TRAIN_BS64_MIN_G": "1000000"}, "rounds_small_fused"),
 ]
 # import torch + the extension, a handful of launches, float64 references
 CHILD_TIMEOUT_S = 240
