@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 
@@ -40,3 +41,152 @@ def robustify_replicas(replicas: torch.Tensor, global_params: torch.Tensor,
     local = replicas[rows]
     glob = global_params[model_of.long()]
     replicas[rows] = norm_diff_clipping(local, glob, norm_bound)
+
+
+# ---------------------------------------------------------------------------
+# robust_fused=1: the SPECIFICATION of the fused clip / noise / server-step
+# path. These functions define the arithmetic (and run as the CPU path);
+# ops/hip/robust_kernels.hip follows them in fp32.
+# ---------------------------------------------------------------------------
+
+SERVER_KINDS = ("avg", "sgd", "adam", "adagrad")
+# torch's defaults, which engine/server_opt.py constructs
+ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8
+ADAGRAD_EPS = 1e-10
+
+
+def clip_scale(norm, bound: float):
+    """min(1, bound / (norm + 1e-12)) — norm_diff_clipping's factor."""
+    if isinstance(norm, torch.Tensor):
+        return torch.clamp(bound / (norm + 1e-12), max=1.0)
+    return np.minimum(1.0, bound / (np.asarray(norm) + 1e-12))
+
+
+def clip_and_accumulate(replicas: torch.Tensor, rows, model_of, weights,
+                        global_params: torch.Tensor, bound: float,
+                        partial: Optional[torch.Tensor] = None):
+    """Clip the listed replica rows IN PLACE to an L2 ball of radius `bound`
+    around their model's global row, and (with `partial` [K, P+1]) add
+    w * clipped into partial[model, :P] and w into partial[model, P] for
+    every pair with w > 0. A row whose factor is 1 keeps its bits; a row
+    with w == 0 is still clipped but adds nothing. Returns the per-model
+    counts (clipped, seen) as int64 arrays [K]."""
+    K, P = global_params.shape
+    rows = torch.as_tensor(np.asarray(rows, dtype=np.int64))
+    mo = torch.as_tensor(np.asarray(model_of, dtype=np.int64))
+    w = torch.as_tensor(np.asarray(weights)).to(replicas.dtype)
+    clipped_n = np.zeros(K, dtype=np.int64)
+    seen_n = np.zeros(K, dtype=np.int64)
+    if rows.numel() == 0:
+        return clipped_n, seen_n
+    local = replicas[rows]
+    glob = global_params[mo]
+    diff = local - glob
+    norm = torch.linalg.vector_norm(diff, dim=1)
+    scale = clip_scale(norm, bound)
+    hit = scale < 1.0
+    out = torch.where(hit.unsqueeze(1), glob + diff * scale.unsqueeze(1),
+                      local)
+    replicas[rows[hit]] = out[hit]
+    if partial is not None:
+        sel = w > 0
+        ws = w[sel].unsqueeze(1)
+        partial.index_add_(0, mo[sel], torch.cat([ws * out[sel], ws], dim=1))
+    np.add.at(seen_n, mo.numpy(), 1)
+    np.add.at(clipped_n, mo.numpy()[hit.numpy()], 1)
+    return clipped_n, seen_n
+
+
+def noise_key(dummy_arg: int, curr_iter: int) -> int:
+    """The 64-bit Philox key of a job's noise: secure_agg.job_key."""
+    from .secure_agg import job_key
+    return job_key(dummy_arg, curr_iter)
+
+
+def gaussian_noise(key: int, ctr: int, K: int, P: int, dtype=np.float64,
+                   models=None, p0: int = 0, p1: Optional[int] = None
+                   ) -> np.ndarray:
+    """Standard normals [K, P] (or the block models x [p0, p1) of them): a
+    pure function of (key, ctr, m, p). Philox4x32-10 with counter
+    (p // 4, m, ctr & 0xffffffff, ctr >> 32) and the two halves of `key`;
+    outputs (x0, x1) give p = 4j, 4j+1 and (x2, x3) give 4j+2, 4j+3 by
+    Box-Muller on u = (x + 0.5) * 2^-32: r = sqrt(-2 ln u_a),
+    z_even = r cos(2 pi u_b), z_odd = r sin(2 pi u_b). Every step is done
+    in `dtype` (float64: the yardstick; float32: what fp32 code gives)."""
+    from .secure_agg import philox4x32
+    dt = np.dtype(dtype).type
+    models = np.arange(K) if models is None else np.asarray(models)
+    p1 = P if p1 is None else p1
+    j0, j1 = p0 // 4, (max(p1, p0 + 1) + 3) // 4
+    nj = j1 - j0
+    ctrs = np.zeros((len(models), nj, 4), dtype=np.uint64)
+    ctrs[:, :, 0] = np.arange(j0, j1, dtype=np.uint64)[None, :]
+    ctrs[:, :, 1] = models.astype(np.uint64)[:, None]
+    ctrs[:, :, 2] = np.uint64(int(ctr) & 0xFFFFFFFF)
+    ctrs[:, :, 3] = np.uint64((int(ctr) >> 32) & 0xFFFFFFFF)
+    k = np.array([key & 0xFFFFFFFF, (key >> 32) & 0xFFFFFFFF],
+                 dtype=np.uint64)
+    x = philox4x32(ctrs, k)                              # [M, nj, 4] uint32
+    u = (x.astype(dt) + dt(0.5)) * dt(2.0 ** -32)
+    out = np.empty((len(models), nj, 4), dtype=dt)
+    two_pi = dt(2.0 * np.pi)
+    for a in (0, 2):
+        r = np.sqrt(dt(-2.0) * np.log(u[:, :, a]))
+        ang = two_pi * u[:, :, a + 1]
+        out[:, :, a] = r * np.cos(ang)
+        out[:, :, a + 1] = r * np.sin(ang)
+    flat = out.reshape(len(models), nj * 4)
+    return np.ascontiguousarray(flat[:, p0 - 4 * j0:p1 - 4 * j0])
+
+
+def new_server_state(kind: str) -> dict:
+    if kind not in SERVER_KINDS:
+        raise ValueError(f"server optimizer '{kind}' is not one of "
+                         f"{list(SERVER_KINDS)}")
+    return {"kind": kind, "step": 0}
+
+
+@torch.no_grad()
+def server_step(kind: str, global_params: torch.Tensor,
+                averaged: torch.Tensor, upd: torch.Tensor, state: dict,
+                lr: float = 1.0, momentum: float = 0.0) -> None:
+    """global <- one server-optimizer step toward `averaged` (in place), as
+    engine/server_opt.py does it with torch.optim at default hyper-
+    parameters: the pseudo-gradient is global - averaged on updated rows and
+    zero elsewhere, ONE step count is shared by the bank, and every row is
+    stepped on every call (so Adam / momentum state of a non-updated row
+    still decays and moves it). 'avg' copies the updated rows."""
+    if kind not in SERVER_KINDS:
+        raise ValueError(f"server optimizer '{kind}' is not one of "
+                         f"{list(SERVER_KINDS)}")
+    u = upd.unsqueeze(1)
+    if kind == "avg":
+        global_params.copy_(torch.where(u, averaged, global_params))
+        return
+    g = torch.where(u, global_params - averaged,
+                    torch.zeros_like(global_params))
+    state["step"] = t = state.get("step", 0) + 1
+    if kind == "sgd":
+        if momentum != 0:
+            if "buf" not in state:
+                state["buf"] = g.clone()
+            else:
+                state["buf"].mul_(momentum).add_(g)
+            g = state["buf"]
+        global_params.add_(g, alpha=-lr)
+    elif kind == "adam":
+        if "m" not in state:
+            state["m"] = torch.zeros_like(global_params)
+            state["v"] = torch.zeros_like(global_params)
+        m, v = state["m"], state["v"]
+        m.add_((g - m) * (1.0 - ADAM_B1))
+        v.mul_(ADAM_B2).add_(g * g * (1.0 - ADAM_B2))
+        step_size = lr / (1.0 - ADAM_B1 ** t)
+        denom = v.sqrt() / ((1.0 - ADAM_B2 ** t) ** 0.5) + ADAM_EPS
+        global_params.add_(m / denom, alpha=-step_size)
+    else:                                                    # adagrad
+        if "sum" not in state:
+            state["sum"] = torch.zeros_like(global_params)
+        state["sum"].add_(g * g)
+        global_params.add_(g / (state["sum"].sqrt() + ADAGRAD_EPS),
+                           alpha=-lr)

@@ -72,9 +72,13 @@ class Config:
     secure_agg_frac_bits: int = 24       # mode 2 fixed-point fraction bits
     robust_norm_bound: float = 0.0       # >0: clip client updates to this L2
     robust_noise: float = 0.0            # >0: Gaussian noise stddev on avg
+    robust_fused: int = 0                # 1: clip / noise / server optimizer
+                                         # on the fused path (HIP kernels on a
+                                         # GPU, the specification on CPU)
     # FedOpt server optimizer ('avg' = plain FedAvg replacement)
     server_optimizer: str = "avg"
     server_lr: float = 1.0
+    server_momentum: float = 0.0         # sgd only (FedAvgM)
 
     def __post_init__(self):
         self.dataset_norm = "MNIST" if self.dataset.lower() == "mnist" else self.dataset
@@ -84,6 +88,9 @@ class Config:
         if not 0 <= self.secure_agg_frac_bits <= 40:
             raise ValueError("secure_agg_frac_bits must lie in [0, 40], got "
                              f"{self.secure_agg_frac_bits}")
+        if self.robust_fused not in (0, 1):
+            raise ValueError("robust_fused must be 0 or 1, got "
+                             f"{self.robust_fused}")
 
     @property
     def is_softcluster(self) -> bool:

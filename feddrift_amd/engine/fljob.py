@@ -302,6 +302,22 @@ class FLJob:
             assert comm.world_size <= _sa.MAX_WORLD, \
                 f"secure_agg=2 supports at most {_sa.MAX_WORLD} ranks"
             self._secagg_base = _sa.job_key(cfg.dummy_arg, self.curr_iter)
+        # robust_fused=1: clipping, noise and the server optimizer run on
+        # the fused path (ops/robust_hip.py)
+        self._robust_fused = cfg.robust_fused == 1
+        if self._robust_fused:
+            from ..comm import robust as _rb
+            from ..ops import robust_hip
+            if cfg.server_optimizer not in _rb.SERVER_KINDS:
+                raise ValueError(
+                    f"robust_fused=1 supports the server optimizers "
+                    f"{list(_rb.SERVER_KINDS)}, got '{cfg.server_optimizer}'")
+            self._server_state = robust_hip.ServerState(
+                cfg.server_optimizer, cfg.server_lr, cfg.server_momentum)
+            self._noise_key = _rb.noise_key(cfg.dummy_arg, self.curr_iter)
+            self._noise_ctr = 0
+            self._clip_counts = robust_hip.new_counts(self.n_models,
+                                                      self.device)
         self.algo.init_iteration(self)
 
     # ------------------------------------------------------------------
@@ -465,8 +481,12 @@ class FLJob:
         K, P = self.n_models, self.n_params
         dev = self.device
         robust = self.cfg.robust_norm_bound > 0
+        # robust_fused=1 keeps the fused launch and clips in a pass of its
+        # own (_robust_clip_fused) between train and aggregate
+        fused_clip = robust and self._robust_fused
         hip = (not self.is_module_path) and self.backend is not ops.mlp_torch \
-            and not robust   # clipping happens between train and aggregate
+            and (fused_clip or not robust)   # clipping happens between
+                                             # train and aggregate
         # ring-arithmetic secure aggregation reads the replicas itself: the
         # launch keeps its fused broadcast but drops the float partial
         ring = self.cfg.secure_agg == 2
@@ -513,9 +533,12 @@ class FLJob:
                 self.spec, self.replicas, rows_t, self.arena.x, self.arena.y,
                 off_t, len_t, self.opt, x_mask=plan.x_mask,
                 in_params=self.global_params,
-                model_of=mo_t, sample_w=None if ring else sw_t,
-                partial=None if ring else self._partial)
+                model_of=mo_t,
+                sample_w=None if ring or fused_clip else sw_t,
+                partial=None if ring or fused_clip else self._partial)
             self._partial_fused = not ring
+            if fused_clip:
+                self._robust_clip_fused(plan, ring)
         else:
             self.sync_replicas()
             rows_t = torch.as_tensor(plan.rows, dtype=torch.int64, device=dev)
@@ -561,12 +584,55 @@ class FLJob:
         fedml_core robustness/robust_aggregation.py:38)."""
         if self.cfg.robust_norm_bound <= 0 or plan.rows.size == 0:
             return
+        if self._robust_fused:
+            ring = self.cfg.secure_agg == 2
+            if not ring:
+                if not getattr(self, "_partial_clean", False):
+                    self._partial.zero_()
+                self._partial_clean = False
+                self._partial_fused = True
+            self._robust_clip_fused(plan, ring)
+            return
         from ..comm.robust import robustify_replicas
         rows_t = torch.as_tensor(plan.rows, dtype=torch.int64,
                                  device=self.device)
         mo = torch.as_tensor(plan.rows % self.n_models, device=self.device)
         robustify_replicas(self.replicas, self.global_params, rows_t, mo,
                            self.cfg.robust_norm_bound)
+
+    def _robust_clip_fused(self, plan: TrainPlan, ring: bool) -> None:
+        """robust_fused=1: one clip pass over the trained rows. It clips
+        them in place and adds their weighted sums into the (zeroed)
+        partial tensor; under secure_agg=2 it only clips, and the ring path
+        reads the replicas as before. The pairs-by-model structure is
+        cached on the plan template."""
+        from ..ops import robust_hip
+        K = self.n_models
+        tmpl = plan.template
+        hit = getattr(tmpl, "_robust", None) if tmpl is not None else None
+        if hit is not None and hit[0] is plan.sample_num:
+            cp = hit[1]
+        else:
+            mo = plan.rows % K
+            cp = robust_hip.ClipPlan(
+                plan.rows, mo, plan.sample_num[plan.rows // K, mo], K)
+            if tmpl is not None:
+                tmpl._robust = (plan.sample_num, cp)
+        robust_hip.clip_accumulate(
+            self.replicas, cp, self.global_params,
+            self.cfg.robust_norm_bound, None if ring else self._partial,
+            self._clip_counts)
+
+    def clip_stats(self) -> np.ndarray:
+        """[K, 2] per-model (clipped, seen) pair counts since the last
+        call, summed across ranks (one small all_reduce); resets them.
+        Zeros unless robust_fused=1 with a norm bound."""
+        if not self._robust_fused:
+            return np.zeros((self.n_models, 2), dtype=np.int64)
+        tot = self._clip_counts.to(torch.float64)
+        self.comm.all_reduce_(tot)
+        self._clip_counts.zero_()
+        return tot.cpu().numpy().astype(np.int64)
 
     def aggregate(self, plan: TrainPlan,
                   model_mask: Optional[np.ndarray] = None) -> torch.Tensor:
@@ -608,6 +674,15 @@ class FLJob:
                 mask_t = torch.as_tensor(
                     np.ascontiguousarray(model_mask, dtype=np.uint8),
                     device=self.device)
+        if self._robust_fused:
+            from ..ops import robust_hip
+            self._noise_ctr += 1
+            totals = robust_hip.apply(
+                self.global_params, partial, mask_t, self._totals,
+                self._server_state, max(self.cfg.robust_noise, 0.0),
+                self._noise_key, self._noise_ctr)
+            self._partial_clean = True
+            return totals
         plain = (self.cfg.server_optimizer == "avg" and
                  self.cfg.robust_noise <= 0)
         if plain and not self.is_module_path and \
@@ -635,9 +710,11 @@ class FLJob:
         if self.cfg.server_optimizer != "avg":
             if getattr(self, "_server_opt", None) is None:
                 from .server_opt import ServerOptimizer
+                kw = {"momentum": self.cfg.server_momentum} \
+                    if self.cfg.server_momentum != 0 else {}
                 self._server_opt = ServerOptimizer(
                     self.global_params, self.cfg.server_optimizer,
-                    self.cfg.server_lr)
+                    self.cfg.server_lr, **kw)
             self._server_opt.step(self.global_params, averaged, upd)
         else:
             self.global_params.copy_(averaged)
@@ -931,6 +1008,14 @@ class FLJob:
                             round_idx)
             self.logger.log({"Test/Acc": test_acc, "Test/Loss": test_loss},
                             round_idx)
+        if self._robust_fused and self.cfg.robust_norm_bound > 0:
+            stats = self.clip_stats()          # all ranks: it all_reduces
+            if self.comm.is_root:
+                for m in range(self.n_models):
+                    if stats[m, 1] > 0:
+                        self.logger.log(
+                            {f"Robust/ClipFrac-m{m}":
+                             stats[m, 0] / stats[m, 1]}, round_idx)
 
     # ------------------------------------------------------------------
     # checkpointing (reference-compatible layout)

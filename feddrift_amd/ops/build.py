@@ -14,8 +14,9 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_DIR, "hip", "feddrift_kernels.hip")
 SRC_CNN = os.path.join(_DIR, "hip", "cnn_kernels.hip")
 SRC_SECAGG = os.path.join(_DIR, "hip", "secagg_kernels.hip")
+SRC_ROBUST = os.path.join(_DIR, "hip", "robust_kernels.hip")
 # the one source list both build functions compile
-SOURCES = [SRC, SRC_CNN, SRC_SECAGG]
+SOURCES = [SRC, SRC_CNN, SRC_SECAGG, SRC_ROBUST]
 BUILD_DIR = os.path.join(_DIR, "hip", "_build")
 MODULE_NAME = "feddrift_hip"
 

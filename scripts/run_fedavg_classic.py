@@ -50,8 +50,10 @@ def main():
     p.add_argument("--client_optimizer", default="adam")
     p.add_argument("--server_optimizer", default="avg")
     p.add_argument("--server_lr", type=float, default=1.0)
+    p.add_argument("--server_momentum", type=float, default=0.0)
     p.add_argument("--robust_norm_bound", type=float, default=0.0)
     p.add_argument("--robust_noise", type=float, default=0.0)
+    p.add_argument("--robust_fused", type=int, default=0)
     p.add_argument("--seed", type=int, default=0)
     a = p.parse_args()
 
@@ -80,8 +82,10 @@ def main():
                  concept_drift_algo="single", retrain_data="win-1",
                  dummy_arg=a.seed, report_client=0,
                  server_optimizer=a.server_optimizer, server_lr=a.server_lr,
+                 server_momentum=a.server_momentum,
                  robust_norm_bound=a.robust_norm_bound,
                  robust_noise=a.robust_noise,
+                 robust_fused=a.robust_fused,
                  log_dir="/tmp/fedavg_classic")
     os.makedirs(cfg.log_dir, exist_ok=True)
     logger = MetricLogger(cfg.log_dir, enabled=comm.is_root, to_file=False)
