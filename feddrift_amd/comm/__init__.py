@@ -78,6 +78,27 @@ class Communicator:
             dist.broadcast(t, src)
         return t
 
+    def all_gather_rows(self, t: torch.Tensor):
+        """Gather the rows of every rank's 2-D tensor `t` (the row counts
+        may differ, the row width may not). Returns (buf, counts): buf is
+        [world_size * max(counts), width], rank r's rows start at
+        r * max(counts) in rank order, padded with zero rows. Works under
+        gloo and RCCL; every rank gets the same buffer."""
+        if not self.distributed:
+            return t, [int(t.shape[0])]
+        cnt = torch.tensor([t.shape[0]], dtype=torch.int64,
+                           device=self.device)
+        cnts = [torch.empty_like(cnt) for _ in range(self.world_size)]
+        dist.all_gather(cnts, cnt)
+        counts = [int(c) for c in torch.cat(cnts).cpu()]
+        most = max(counts)
+        mine = t.new_zeros(most, t.shape[1])
+        mine[:t.shape[0]] = t
+        parts = [torch.empty_like(mine) for _ in range(self.world_size)]
+        if most:
+            dist.all_gather(parts, mine)
+        return torch.cat(parts, dim=0), counts
+
     def all_gather_object(self, obj):
         if not self.distributed:
             return [obj]

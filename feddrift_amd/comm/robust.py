@@ -139,6 +139,87 @@ def gaussian_noise(key: int, ctr: int, K: int, P: int, dtype=np.float64,
     return np.ascontiguousarray(flat[:, p0 - 4 * j0:p1 - 4 * j0])
 
 
+# ---------------------------------------------------------------------------
+# robust_agg = trimmed_mean | median: the SPECIFICATION of the order-
+# statistic aggregation (numpy). ops/hip/orderstat_kernels.hip follows it.
+# The statistic is unweighted over a model's participants (its pairs with an
+# aggregation weight > 0): a client can lie about its sample count as easily
+# as about its parameters, so the weight only decides participation.
+# ---------------------------------------------------------------------------
+
+ORDER_KINDS = ("mean", "trimmed_mean", "median")
+
+
+def ordered_key(x) -> np.ndarray:
+    """uint32 keys of float32 values whose unsigned order is the total order
+    -NaN < -Inf < ... < -0 < +0 < ... < +Inf < +NaN: ~u under a set sign
+    bit, u | 0x80000000 otherwise. Agrees with np.sort on finite values."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u,
+                    u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def trim_count(kind: str, frac: float, n: int) -> int:
+    """Rows dropped at either end of every coordinate's sorted column. At
+    least one value always survives."""
+    n = int(n)
+    most = max(n - 1, 0) // 2
+    if kind == "median":
+        return most
+    if kind == "trimmed_mean":
+        return min(int(np.floor(frac * n + 1e-9)), most)
+    raise ValueError(f"'{kind}' is not an order statistic "
+                     f"({list(ORDER_KINDS[1:])})")
+
+
+def order_stat_mean(values, k: int, dtype=np.float64) -> np.ndarray:
+    """Per column of values [n, P] (float32): sort by ordered_key, keep
+    sorted positions k .. n-k-1, sum these s = n - 2k survivors in sorted
+    order in `dtype`, divide by s. s = 1 returns the selected element
+    itself (no arithmetic: its bits survive), s = 2 returns (a + b) * 0.5."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    n = v.shape[0]
+    k = int(k)
+    s = n - 2 * k
+    assert k >= 0 and s >= 1, (n, k)
+    dt = np.dtype(dtype).type
+    order = np.argsort(ordered_key(v), axis=0, kind="stable")
+    srt = np.take_along_axis(v, order, axis=0)[k:n - k]
+    with np.errstate(all="ignore"):
+        if s == 1:
+            return srt[0].astype(dt)
+        if s == 2:
+            return (srt[0].astype(dt) + srt[1].astype(dt)) * dt(0.5)
+        acc = srt[0].astype(dt)
+        for i in range(1, s):
+            acc = acc + srt[i].astype(dt)
+        return acc / dt(s)
+
+
+def order_stat_aggregate(replicas, rows, model_of, weights, K: int,
+                         kind: str, frac: float, out, dtype=np.float32):
+    """out[m] <- order_stat_mean of model m's participant rows (the listed
+    pairs with weight > 0), for every model with a participant; other rows
+    of `out` ([K, P], numpy or a CPU tensor, written through a view) keep
+    their bits, and `replicas` is only read. Returns (n [K], k [K])."""
+    bank = replicas.detach().numpy() if isinstance(replicas, torch.Tensor) \
+        else np.asarray(replicas)
+    dst = out.detach().numpy() if isinstance(out, torch.Tensor) else out
+    rows = np.asarray(rows, dtype=np.int64)
+    mo = np.asarray(model_of, dtype=np.int64)
+    sel = np.asarray(weights) > 0
+    n_out = np.zeros(K, dtype=np.int64)
+    k_out = np.zeros(K, dtype=np.int64)
+    for m in range(K):
+        r = rows[sel & (mo == m)]
+        n_out[m] = len(r)
+        if len(r) == 0:
+            continue
+        k_out[m] = trim_count(kind, frac, len(r))
+        dst[m] = order_stat_mean(bank[r], k_out[m], dtype)
+    return n_out, k_out
+
+
 def new_server_state(kind: str) -> dict:
     if kind not in SERVER_KINDS:
         raise ValueError(f"server optimizer '{kind}' is not one of "

@@ -75,6 +75,12 @@ class Config:
     robust_fused: int = 0                # 1: clip / noise / server optimizer
                                          # on the fused path (HIP kernels on a
                                          # GPU, the specification on CPU)
+    robust_agg: str = "mean"             # mean|trimmed_mean|median: the
+                                         # per-coordinate statistic over a
+                                         # model's uploads (unweighted for
+                                         # the two order statistics)
+    robust_trim_frac: float = 0.1        # trimmed_mean: share dropped at
+                                         # either end, in [0, 0.5)
     # FedOpt server optimizer ('avg' = plain FedAvg replacement)
     server_optimizer: str = "avg"
     server_lr: float = 1.0
@@ -91,6 +97,17 @@ class Config:
         if self.robust_fused not in (0, 1):
             raise ValueError("robust_fused must be 0 or 1, got "
                              f"{self.robust_fused}")
+        if self.robust_agg not in ("mean", "trimmed_mean", "median"):
+            raise ValueError("robust_agg must be one of mean, trimmed_mean, "
+                             f"median, got '{self.robust_agg}'")
+        if not 0.0 <= self.robust_trim_frac < 0.5:
+            raise ValueError("robust_trim_frac must lie in [0, 0.5), got "
+                             f"{self.robust_trim_frac}")
+        if self.robust_agg != "mean" and self.secure_agg != 0:
+            raise ValueError(
+                f"robust_agg='{self.robust_agg}' cannot run with secure_agg="
+                f"{self.secure_agg}: an order statistic needs the individual "
+                "uploads, and secure aggregation exists to hide them")
 
     @property
     def is_softcluster(self) -> bool:

@@ -489,7 +489,8 @@ class FLJob:
                                              # train and aggregate
         # ring-arithmetic secure aggregation reads the replicas itself: the
         # launch keeps its fused broadcast but drops the float partial
-        ring = self.cfg.secure_agg == 2
+        # (an order statistic reads them too: robust_agg != "mean")
+        ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
         if self._partial is None or self._partial.shape[0] != K:
             self._partial = torch.zeros(K, P + 1, device=dev)
             self._totals = torch.zeros(K, device=dev)
@@ -585,7 +586,7 @@ class FLJob:
         if self.cfg.robust_norm_bound <= 0 or plan.rows.size == 0:
             return
         if self._robust_fused:
-            ring = self.cfg.secure_agg == 2
+            ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
             if not ring:
                 if not getattr(self, "_partial_clean", False):
                     self._partial.zero_()
@@ -603,9 +604,9 @@ class FLJob:
     def _robust_clip_fused(self, plan: TrainPlan, ring: bool) -> None:
         """robust_fused=1: one clip pass over the trained rows. It clips
         them in place and adds their weighted sums into the (zeroed)
-        partial tensor; under secure_agg=2 it only clips, and the ring path
-        reads the replicas as before. The pairs-by-model structure is
-        cached on the plan template."""
+        partial tensor; under secure_agg=2 or an order statistic (`ring`)
+        it only clips, and that path reads the replicas itself. The
+        pairs-by-model structure is cached on the plan template."""
         from ..ops import robust_hip
         K = self.n_models
         tmpl = plan.template
@@ -650,6 +651,13 @@ class FLJob:
         all_reduce is shared."""
         K, P = self.n_models, self.n_params
         partial = self._partial
+        if self.cfg.robust_agg != "mean":
+            # the statistic takes the weighted sums' place with a total of
+            # 1 (dividing by 1 is exact); the true totals are put back last
+            sum_w = self._order_stat_partial(plan, partial)
+            totals = self._apply_partial(partial, model_mask)
+            totals.copy_(sum_w)
+            return totals
         if self.cfg.secure_agg == 2:
             self._secure_ring_partial(plan, partial)
         else:
@@ -665,6 +673,14 @@ class FLJob:
             if self.cfg.secure_agg:
                 self._apply_secure_masks(plan, partial)
             self.comm.all_reduce_(partial)
+        return self._apply_partial(partial, model_mask)
+
+    def _apply_partial(self, partial: torch.Tensor,
+                       model_mask: Optional[np.ndarray]) -> torch.Tensor:
+        """Everything after the all_reduce: average the reduced [K, P+1]
+        sums under the skip rules and the mask, add the noise, take the
+        server step. Returns the totals (slot P)."""
+        P = self.n_params
         totals = partial[:, P]
         mask_t = None
         if model_mask is not None:
@@ -719,6 +735,60 @@ class FLJob:
         else:
             self.global_params.copy_(averaged)
         return totals
+
+    def _order_stat_partial(self, plan: TrainPlan,
+                            partial: torch.Tensor) -> torch.Tensor:
+        """robust_agg = trimmed_mean | median: partial[m, :P] <- the
+        coordinate-wise statistic over model m's participants (the trained
+        pairs with a positive weight, of all ranks), partial[m, P] <- 1 for
+        a model with participants and 0 otherwise. At world size 1 the
+        kernel reads the replica bank through the plan's row list; above,
+        every rank gathers all participant rows and computes the same
+        result from the same buffer. Returns the true per-model sum of
+        weights over all ranks."""
+        from ..ops import orderstat_hip
+        K, P = self.n_models, self.n_params
+        cfg = self.cfg
+        dev = self.device
+        tmpl = plan.template
+        hit = getattr(tmpl, "_orderstat", None) if tmpl is not None else None
+        if hit is not None and hit[0] is plan.sample_num:
+            op, sum_w = hit[1], hit[2]
+        else:
+            # per-template constants: uploaded once, reused every round
+            mo = plan.rows % K
+            sn = np.asarray(plan.sample_num)
+            w = sn[plan.rows // K, mo] if plan.rows.size else \
+                np.zeros(0, np.float32)
+            op = orderstat_hip.OrderStatPlan(
+                plan.rows, mo, w, K, cfg.robust_agg, cfg.robust_trim_frac)
+            sum_w = torch.as_tensor(sn, dtype=torch.float32, device=dev) \
+                .reshape(-1, K).sum(dim=0)
+            if tmpl is not None:
+                tmpl._orderstat = (plan.sample_num, op, sum_w)
+        bank = self.replicas
+        if self.comm.distributed:
+            sum_w = self.comm.all_reduce_(sum_w.clone())
+            mine = torch.as_tensor(op.rows, device=dev)
+            buf, counts = self.comm.all_gather_rows(self.replicas[mine])
+            ids, _ = self.comm.all_gather_rows(
+                torch.as_tensor(op.models, device=dev).unsqueeze(1))
+            most = max(counts)
+            at = np.concatenate([r * most + np.arange(c)
+                                 for r, c in enumerate(counts)])
+            models = ids[:, 0].cpu().numpy()[at]
+            op = orderstat_hip.OrderStatPlan(
+                at, models, np.ones(len(at), np.float32), K,
+                cfg.robust_agg, cfg.robust_trim_frac)
+            bank = buf
+        partial.zero_()
+        orderstat_hip.aggregate(bank, op, partial[:, :P])
+        if getattr(op, "_has", None) is None:
+            op._has = torch.as_tensor((op.n > 0).astype(np.float32),
+                                      device=dev)
+        partial[:, P] = op._has
+        self._partial_clean = False
+        return sum_w
 
     def _apply_secure_masks(self, plan: TrainPlan,
                             partial: torch.Tensor) -> None:
