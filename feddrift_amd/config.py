@@ -85,9 +85,16 @@ class Config:
     server_optimizer: str = "avg"
     server_lr: float = 1.0
     server_momentum: float = 0.0         # sgd only (FedAvgM)
+    # FedProx proximal local training: every executed local step adds
+    # mu * (w - w0) to the gradient, w0 = the global model the client got
+    # this round (0 = plain local training, bit for bit)
+    fedprox_mu: float = 0.0
 
     def __post_init__(self):
         self.dataset_norm = "MNIST" if self.dataset.lower() == "mnist" else self.dataset
+        if not (self.fedprox_mu >= 0.0 and self.fedprox_mu != float("inf")):
+            raise ValueError("fedprox_mu must be finite and >= 0, got "
+                             f"{self.fedprox_mu}")
         if self.secure_agg_degree < 0 or self.secure_agg_degree % 2:
             raise ValueError("secure_agg_degree must be even and >= 0, got "
                              f"{self.secure_agg_degree}")

@@ -272,11 +272,12 @@ class FLJob:
         self.replicas = torch.zeros(nW * self.n_models, P, device=self.device)
         if self.is_module_path:
             self.opt = self.mod_engine.make_opt_state(
-                cfg.client_optimizer, nW * self.n_models, cfg.lr, cfg.wd)
+                cfg.client_optimizer, nW * self.n_models, cfg.lr, cfg.wd,
+                mu=cfg.fedprox_mu)
         else:
             self.opt = ops.mlp_torch.make_opt_state(
                 cfg.client_optimizer, nW * self.n_models, P, cfg.lr, cfg.wd,
-                self.device)
+                self.device, mu=cfg.fedprox_mu)
 
         # per-rank batch-pick RNG (statistical parity; reference draws on
         # each worker process's own global np RNG)

@@ -29,6 +29,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip_loader
+from .mlp_torch import check_mu
 
 # CNN_DropOut geometry, the fc1 K-split count and the eval modes are
 # defined once, in cnn_kernels.hip, and exported by the extension. The
@@ -80,9 +81,11 @@ class CnnHipEngine:
         self._ws = None
 
     # -- optimizer state (same layout as the module engines) -------------
-    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float):
+    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float,
+                       mu: float = 0.0):
         from .mlp_torch import make_opt_state
-        return make_opt_state(kind, n_rows, self.P, lr, wd, self.device)
+        return make_opt_state(kind, n_rows, self.P, lr, wd, self.device,
+                              mu=mu)
 
     # -- training ---------------------------------------------------------
     def _dropout_ps(self):
@@ -192,6 +195,13 @@ class CnnHipEngine:
         self._seed_counter += 1
         seed = (self._seed_counter * 0x100000001B3) & ((1 << 63) - 1)
         xm = x_mask.contiguous() if x_mask is not None else None
+        # FedProx: the kernel reads pair g's anchor as row rows[g] % K of
+        # the global bank, so a chunk needs no anchor slice of its own
+        mu = check_mu(opt.get("mu", 0.0))
+        anchor = None
+        if mu != 0.0:
+            assert global_params.shape[0] == n_models
+            anchor = global_params.contiguous()
         for e in range(E):
             self.mod.cnn_train_epoch(
                 work, ws["grad"], rows, x_arena, y_arena,
@@ -205,7 +215,8 @@ class CnnHipEngine:
                 opt["vmax"] if adam else None,
                 opt["t"] if adam else None,
                 opt["lr"], float(opt.get("wd", 0.0)),
-                p1, p2, seed, g_base, B, self.O, ws["w2ms"])
+                p1, p2, seed, g_base, B, self.O, ws["w2ms"],
+                mu, anchor)
         replicas[rows] = work
 
     # -- evaluation -------------------------------------------------------

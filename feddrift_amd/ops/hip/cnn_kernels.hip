@@ -91,6 +91,11 @@ struct CnnArgs {
   int* __restrict__ t;
   const float* __restrict__ lr;      // [n_rows]
   float wd;
+  // FedProx: mu > 0 pulls every executed step towards the pair's round
+  // start, row rows[g] % K of the global bank (never written by a round)
+  const float* __restrict__ anchor;  // [K, P] global models, or null
+  float mu;
+  int K;
   float p1, p2;                      // dropout probs
   unsigned long long seed;           // per (round, epoch)
   long long g0;                      // global pair-index base (mask hash)
@@ -1270,8 +1275,12 @@ void cnn_conv1_wgrad_reduce(CnnArgs a) {
 // 28 scalar loads the per-element branch produced.
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
-extern "C" __global__ __launch_bounds__(WG)
-void cnn_opt_step(CnnArgs a) {
+// PROX (FedProx, mu != 0) adds mu * (w - w0) to the gradient, w0 the
+// pair's row of the global bank. It is a template parameter, not a runtime
+// test: the four anchor registers cost cnn_opt_step a wave of occupancy
+// (76 VGPRs against 72), which the mu = 0 kernel does not pay.
+template <bool PROX>
+__device__ __forceinline__ void cnn_opt_step_body(const CnnArgs& a) {
   const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
   const long long pv = a.P / 4;          // float4 body; tail scalar
   const long long total = (long long)a.G * pv;
@@ -1284,15 +1293,26 @@ void cnn_opt_step(CnnArgs a) {
     const long long pp = (qv - (long long)g * pv) * 4;
     const long long q0 = (long long)g * a.P + pp;
     const bool tail = (qv - (long long)g * pv == pv - 1);
+    const float* __restrict__ w0 =
+        PROX ? a.anchor + (row % a.K) * (long long)a.P : nullptr;
     if (a.opt == OPT_SGD) {
       f4u wv = *(const f4u*)(a.work + q0);
-      const f4u gr = *(const f4u*)(a.grad + q0);
+      f4u gr = *(const f4u*)(a.grad + q0);
+      if constexpr (PROX) {
+        const f4u av = *(const f4u*)(w0 + pp);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gr[j] += a.mu * (wv[j] - av[j]);
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) wv[j] -= lr_ * gr[j];
       *(f4u*)(a.work + q0) = wv;
       if (tail)
-        for (long long q = q0 + 4; q < (long long)(g + 1) * a.P; ++q)
-          a.work[q] -= lr_ * a.grad[q];
+        for (long long q = q0 + 4; q < (long long)(g + 1) * a.P; ++q) {
+          float gs = a.grad[q];
+          if constexpr (PROX)
+            gs += a.mu * (a.work[q] - w0[q - (long long)g * a.P]);
+          a.work[q] -= lr_ * gs;
+        }
       continue;
     }
     const int tnew = a.t[row] + 1;       // tick kernel commits after
@@ -1300,7 +1320,12 @@ void cnn_opt_step(CnnArgs a) {
     const float bc2 = 1.f - powf(b2, (float)tnew);
     const long long s0 = row * a.P + pp;
     f4u wv = *(const f4u*)(a.work + q0);
-    const f4u gr0 = *(const f4u*)(a.grad + q0);
+    f4u gr0 = *(const f4u*)(a.grad + q0);
+    if constexpr (PROX) {
+      const f4u av = *(const f4u*)(w0 + pp);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gr0[j] += a.mu * (wv[j] - av[j]);
+    }
     f4u mo = *(const f4u*)(a.m + s0);
     f4u vo = *(const f4u*)(a.v + s0);
     f4u vm = *(const f4u*)(a.vmax + s0);
@@ -1322,7 +1347,10 @@ void cnn_opt_step(CnnArgs a) {
     if (tail) {
       for (long long q = q0 + 4; q < (long long)(g + 1) * a.P; ++q) {
         const long long gp = row * a.P + (q - (long long)g * a.P);
-        const float gr = a.grad[q] + a.wd * a.work[q];
+        float gs = a.grad[q];
+        if constexpr (PROX)
+          gs += a.mu * (a.work[q] - w0[q - (long long)g * a.P]);
+        const float gr = gs + a.wd * a.work[q];
         const float mn = b1 * a.m[gp] + (1.f - b1) * gr;
         const float vn = b2 * a.v[gp] + (1.f - b2) * gr * gr;
         a.m[gp] = mn;
@@ -1334,6 +1362,11 @@ void cnn_opt_step(CnnArgs a) {
     }
   }
 }
+
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_opt_step(CnnArgs a) { cnn_opt_step_body<false>(a); }
+extern "C" __global__ __launch_bounds__(WG)
+void cnn_opt_step_prox(CnnArgs a) { cnn_opt_step_body<true>(a); }
 
 extern "C" __global__ void cnn_opt_tick(CnnArgs a) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1549,10 +1582,27 @@ void cnn_train_epoch_impl(
     c10::optional<torch::Tensor> m, c10::optional<torch::Tensor> v,
     c10::optional<torch::Tensor> vmax, c10::optional<torch::Tensor> t,
     torch::Tensor lr, double wd, double p1, double p2,
-    int64_t seed, int64_t g0, int64_t B, int64_t O, int64_t w2ms) {
+    int64_t seed, int64_t g0, int64_t B, int64_t O, int64_t w2ms,
+    double mu, c10::optional<torch::Tensor> anchor) {
   const int G = rows.size(0);
   if (G == 0) return;
+  TORCH_CHECK(mu >= 0.0 && std::isfinite(mu),
+              "cnn_train_epoch: fedprox mu=", mu,
+              " must be finite and >= 0");
   CnnArgs a;
+  a.mu = (float)mu;
+  a.anchor = nullptr;
+  a.K = 1;
+  if (a.mu != 0.f) {
+    TORCH_CHECK(anchor.has_value() && anchor->is_cuda() &&
+                anchor->dtype() == torch::kFloat32 &&
+                anchor->is_contiguous() && anchor->dim() == 2 &&
+                anchor->size(1) == work.size(1) && anchor->size(0) >= 1,
+                "cnn_train_epoch: fedprox needs the contiguous f32 [K, P] "
+                "global bank as anchor");
+    a.anchor = anchor->data_ptr<float>();
+    a.K = (int)anchor->size(0);
+  }
   a.work = work.data_ptr<float>();
   a.grad = grad.data_ptr<float>();
   a.rows = rows.data_ptr<int64_t>();
@@ -1641,7 +1691,10 @@ void cnn_train_epoch_impl(
   LB(cnn_conv1_wgrad_part, GB);
   L(cnn_conv1_wgrad_reduce, (long long)G * 320);
   // optimizer
-  L(cnn_opt_step, (long long)G * a.P);
+  if (a.mu != 0.f)
+    L(cnn_opt_step_prox, (long long)G * a.P);
+  else
+    L(cnn_opt_step, (long long)G * a.P);
   LB(cnn_opt_tick, (G + WG - 1) / WG);
   TORCH_CHECK(hipGetLastError() == hipSuccess, "cnn_train_epoch launch");
 }

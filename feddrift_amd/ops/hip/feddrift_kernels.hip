@@ -12,7 +12,8 @@
 //    accumulator live in LDS for the entire E-step optimizer loop; each
 //    step stages its minibatch chunk through LDS, computes forward +
 //    backward with per-thread sample parallelism, reduces gradients with a
-//    per-thread ownership partition (no atomics), and applies the
+//    per-thread ownership partition (no atomics: shared entries add
+//    their partial sums in a fixed order), and applies the
 //    SGD/Adam(amsgrad, wd) update in-place. Adam state stays in HBM.
 //  * mlp_eval_kernel: ONE launch per accuracy/loss sweep (the K-models x
 //    C-clients matrices, prequential testing). One workgroup per data
@@ -71,8 +72,18 @@ struct TrainArgs {
   int* __restrict__ t;               // [R]
   const float* __restrict__ lr;      // [R]
   float wd;
+  float mu;                          // FedProx coefficient, 0 = off
   int E, D, H, O, P, kind, opt, BC;
 };
+
+// FedProx anchor w0 of pair g: the row the weights were staged from
+// (stage_weights). Nothing writes either source before write_back, so the
+// anchor is re-read from global memory at each step and costs no LDS.
+__device__ __forceinline__ const float* prox_anchor(const TrainArgs& a, int g,
+                                                    int64_t row) {
+  return a.in_params ? a.in_params + (int64_t)a.model_of[g] * a.P
+                     : a.params + row * a.P;
+}
 
 __device__ __forceinline__ float block_reduce_sum(float val, float* scratch) {
   // wave shuffle reduce then cross-wave via LDS (4 waves / 256 threads)
@@ -106,9 +117,17 @@ __device__ __forceinline__ void stage_weights(const TrainArgs& a, int g,
   __syncthreads();
 }
 
-__device__ __forceinline__ void opt_update(const TrainArgs& a, int64_t row,
-                                           float* w, const float* grad) {
+__device__ __forceinline__ void opt_update(const TrainArgs& a, int g,
+                                           int64_t row, float* w,
+                                           float* grad) {
   const int tid = threadIdx.x;
+  if (a.mu != 0.f) {
+    // proximal pull, folded into the gradient by the thread that consumes
+    // entry p below (same p -> tid mapping: no barrier in between)
+    const float* w0 = prox_anchor(a, g, row);
+    for (int p = tid; p < a.P; p += THREADS)
+      grad[p] += a.mu * (w[p] - w0[p]);
+  }
   if (a.opt == OPT_SGD) {
     const float lr_ = a.lr[row];
     for (int p = tid; p < a.P; p += THREADS) w[p] -= lr_ * grad[p];
@@ -159,6 +178,9 @@ void mlp_train_kernel(TrainArgs a) {
   const int tid = threadIdx.x;
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  // per-entry partial gradient sums of phase E (2 KB beside the 150 KB
+  // dynamic budget; the 160 KB of a CU hold both)
+  __shared__ float gpart[2 * THREADS];
   float* w = lds;              // [P]
   float* grad = w + a.P;       // [P]
   float* xb = grad + a.P;      // [BC, D]
@@ -274,8 +296,9 @@ void mlp_train_kernel(TrainArgs a) {
       }
 
       // phase E: gradient accumulation. NSUB threads share each parameter
-      // entry, each summing a sample stride, then one LDS atomicAdd —
-      // P*NSUB work items keep the block busy for small P
+      // entry, each summing a sample stride; the NSUB partial sums then
+      // meet in sub order (below) — P*NSUB work items keep the block busy
+      // for small P
       {
         int nsub = (2 * THREADS) / (a.P > 0 ? a.P : 1);
         nsub = nsub < 1 ? 1 : (nsub > 32 ? 32 : nsub);
@@ -310,14 +333,28 @@ void mlp_train_kernel(TrainArgs a) {
               for (int i = sub; i < bc; i += nsub) acc += dzo[i * a.O + o];
             }
           }
-          atomicAdd(&grad[p], acc);
+          // nsub == 1: this thread owns entry p. Otherwise the partial
+          // sums wait in gpart (q = sub * P + p < P * nsub <= 2 * THREADS)
+          // and are added in sub order below: LDS atomics would land in
+          // whatever order the waves arrive, and a launch would not
+          // repeat bit for bit
+          if (nsub == 1) grad[p] += acc;
+          else gpart[q] = acc;
+        }
+        if (nsub > 1) {
+          __syncthreads();
+          for (int p = tid; p < a.P; p += THREADS) {
+            float gsum = grad[p];
+            for (int s = 0; s < nsub; ++s) gsum += gpart[s * a.P + p];
+            grad[p] = gsum;
+          }
         }
       }
       __syncthreads();
     }
 
     // optimizer update (matches torch.optim exactly; see ops/mlp_torch.py)
-    opt_update(a, row, w, grad);
+    opt_update(a, g, row, w, grad);
     __syncthreads();
   }
 
@@ -327,8 +364,9 @@ void mlp_train_kernel(TrainArgs a) {
 // ---------------------------------------------------------------------------
 // specialized small-MLP training kernel: the whole per-sample pipeline and
 // the per-thread gradient accumulators live in REGISTERS (compile-time
-// D/H/O, fully unrolled); gradients reduce by wave shuffles + one LDS
-// atomic per wave. This is the SEA/SINE/CIRCLE flagship path — the generic
+// D/H/O, fully unrolled); gradients reduce by wave shuffles, then one LDS
+// add per entry (single-wave blocks) or the waves' sums added in wave
+// order (256-thread blocks). This is the SEA/SINE/CIRCLE flagship path — the generic
 // kernel above stays latency-bound on LDS round trips for these shapes.
 // ---------------------------------------------------------------------------
 
@@ -484,13 +522,38 @@ void mlp_train_small_kernel(TrainArgs a) {
 #pragma unroll
       for (int p = 0; p < TP; ++p) gacc[p] += sh[p];
     }
-    if (lane == 0) {
+    if constexpr (BS == 64) {
+      if (lane == 0) {
 #pragma unroll
-      for (int p = 0; p < TP; ++p) atomicAdd(&grad[p], gacc[p]);
+        for (int p = 0; p < TP; ++p) atomicAdd(&grad[p], gacc[p]);
+      }
+    } else {
+      // several waves: their sums meet in wave order, not in the order the
+      // LDS atomics happen to land, so a launch repeats bit for bit
+      __shared__ float wsum[BS / 64][TP];
+      if (lane == 0) {
+#pragma unroll
+        for (int p = 0; p < TP; ++p) wsum[tid >> 6][p] = gacc[p];
+      }
+      __syncthreads();
+      for (int p = tid; p < TP; p += BS) {
+        float s = wsum[0][p];
+#pragma unroll
+        for (int wv = 1; wv < BS / 64; ++wv) s += wsum[wv][p];
+        grad[p] = s;
+      }
     }
     __syncthreads();
 
     // optimizer step, all state in LDS (numerics match ops/mlp_torch.py)
+    if (a.mu != 0.f) {
+      // FedProx pull (wave-uniform branch); entry p is folded in by the
+      // thread that steps it below. The anchor row is a few dozen
+      // L2-resident floats.
+      const float* w0 = prox_anchor(a, g, row);
+      for (int p = tid; p < TP; p += BS)
+        grad[p] += a.mu * (w[p] - w0[p]);
+    }
     if (!adam) {
       const float lr_ = a.lr[row];
       for (int p = tid; p < TP; p += BS) w[p] -= lr_ * grad[p];
@@ -982,11 +1045,13 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
                      c10::optional<torch::Tensor> in_params,
                      c10::optional<torch::Tensor> model_of,
                      c10::optional<torch::Tensor> sample_w,
-                     c10::optional<torch::Tensor> partial) {
+                     c10::optional<torch::Tensor> partial, double mu) {
   const int G = rows.size(0);
   if (G == 0) return;
   TORCH_CHECK(O >= 1 && O <= 64,
               "train_fused: O=", O, " outside the per-sample float[64] logits");
+  TORCH_CHECK(mu >= 0.0 && std::isfinite(mu),
+              "train_fused: fedprox mu=", mu, " must be finite and >= 0");
   check_f32_2d(params, "params");
   const int P = params.size(1);
   const int E = step_off.size(1);
@@ -1021,6 +1086,7 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
   args.t = adam ? t->data_ptr<int>() : nullptr;
   args.lr = lr.data_ptr<float>();
   args.wd = (float)wd;
+  args.mu = (float)mu;
   args.E = E; args.D = (int)D; args.H = (int)H; args.O = (int)O;
   args.P = P; args.kind = (int)kind; args.opt = adam ? OPT_ADAM : OPT_SGD;
   args.BC = BC;

@@ -59,10 +59,13 @@ def train_fused(spec: MLPSpec, params_all: torch.Tensor, rows: torch.Tensor,
     if rows.numel() == 0:
         return
     if not _fits_train(spec):
+        anchor = None
         if in_params is not None:
-            params_all[rows] = in_params[model_of.long()]
+            anchor = in_params[model_of.long()]
+            params_all[rows] = anchor
         mlp_torch.train_fused(spec, params_all, rows, x_arena, y_arena,
-                              step_off, step_len, opt, x_mask=x_mask)
+                              step_off, step_len, opt, x_mask=x_mask,
+                              anchor=anchor)
         if partial is not None and sample_w is not None:
             P = params_all.shape[1]
             mo = model_of.long()
@@ -83,7 +86,8 @@ def train_fused(spec: MLPSpec, params_all: torch.Tensor, rows: torch.Tensor,
         opt["vmax"] if adam else None,
         opt["t"] if adam else None,
         opt["lr"], float(opt.get("wd", 0.0)),
-        in_params, model_of, sample_w, partial)
+        in_params, model_of, sample_w, partial,
+        mlp_torch.check_mu(opt.get("mu", 0.0)))
 
 
 def apply_aggregate(global_params: torch.Tensor, partial: torch.Tensor,

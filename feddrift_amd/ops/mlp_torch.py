@@ -23,11 +23,20 @@ ADAM_B2 = 0.999
 ADAM_EPS = 1e-8
 
 
+def check_mu(mu) -> float:
+    """FedProx coefficient: a finite float >= 0, else ValueError."""
+    mu = float(mu)
+    if not (mu >= 0.0 and mu != float("inf")):
+        raise ValueError(f"fedprox_mu must be finite and >= 0, got {mu}")
+    return mu
+
+
 def make_opt_state(kind: str, n_pairs: int, n_params: int, lr: float,
-                   wd: float, device, dtype=torch.float32) -> Dict:
+                   wd: float, device, dtype=torch.float32,
+                   mu: float = 0.0) -> Dict:
     st = {"kind": kind,
           "lr": torch.full((n_pairs,), lr, device=device, dtype=dtype),
-          "wd": wd}
+          "wd": wd, "mu": check_mu(mu)}
     if kind == "adam":
         z = dict(device=device, dtype=dtype)
         st["m"] = torch.zeros(n_pairs, n_params, **z)
@@ -103,7 +112,8 @@ def train_fused(spec: MLPSpec,
                 step_off: torch.Tensor,        # [G, E] int64 window starts
                 step_len: torch.Tensor,        # [G, E] int64 window lengths
                 opt: Dict,
-                x_mask: Optional[torch.Tensor] = None  # [G, D] input mask
+                x_mask: Optional[torch.Tensor] = None,  # [G, D] input mask
+                anchor: Optional[torch.Tensor] = None   # [G, P] prox anchor
                 ) -> None:
     """E local optimizer steps per pair, each on its own minibatch window.
 
@@ -114,12 +124,21 @@ def train_fused(spec: MLPSpec,
     state advance — reference FedAvgEnsTrainerExp.py:73-74 `continue`).
     x_mask (KUE feature masks, FedAvgEnsTrainerKue.py:65-97) multiplies the
     inputs elementwise before the forward pass.
+
+    opt["mu"] > 0 is the FedProx proximal objective (Li et al., MLSys 2020)
+    ell(w) + mu/2 |w - w0|^2: every EXECUTED step hands the optimizer
+    grad + mu * (w - w0), with w the current weights and w0 the pair's
+    `anchor` row (default: the weights this call starts from). A skipped
+    step gets no pull either. mu == 0 (or no key) adds nothing at all.
     """
     G, E = step_off.shape
     if G == 0:
         return
     dev = params_all.device
     params = params_all[rows]
+    mu = check_mu(opt.get("mu", 0.0))
+    if mu != 0.0:
+        anchor = params.clone() if anchor is None else anchor.to(params.dtype)
     if opt["kind"] == "adam":
         st = {"m": opt["m"][rows], "v": opt["v"][rows],
               "vmax": opt["vmax"][rows], "t": opt["t"][rows]}
@@ -146,7 +165,8 @@ def train_fused(spec: MLPSpec,
             dz2 = torch.softmax(z2, dim=-1)
             dz2.scatter_add_(-1, y.unsqueeze(-1),
                              -torch.ones_like(dz2[..., :1]))
-            dz2 = dz2 * (mask.unsqueeze(-1) / ln.reshape(G, 1, 1))
+            dz2 = dz2 * (mask.unsqueeze(-1).to(params.dtype)
+                         / ln.reshape(G, 1, 1))
             G_ = params.shape[0]
             w2 = params[:, spec.off_w2:spec.off_b2].reshape(G_, spec.o, spec.h)
             dw2 = torch.bmm(dz2.transpose(1, 2), a)             # [G,O,H]
@@ -162,11 +182,15 @@ def train_fused(spec: MLPSpec,
             dp = torch.softmax(p, dim=-1)
             dp.scatter_add_(-1, y.unsqueeze(-1),
                             -torch.ones_like(dp[..., :1]))
-            dp = dp * (mask.unsqueeze(-1) / ln.reshape(G, 1, 1))
+            dp = dp * (mask.unsqueeze(-1).to(params.dtype)
+                       / ln.reshape(G, 1, 1))
             dz = dp * p * (1 - p)
             dw = torch.bmm(dz.transpose(1, 2), x)
             db = dz.sum(dim=1)
             grads = torch.cat([dw.reshape(G, -1), db], dim=1)
+
+        if mu != 0.0:
+            grads = grads + mu * (params - anchor)
 
         sel = ln > 0
         if bool(sel.all()):

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..models.generic_packer import ModulePacker
-from .mlp_torch import ADAM_B1, ADAM_B2, ADAM_EPS
+from .mlp_torch import ADAM_B1, ADAM_B2, ADAM_EPS, check_mu
 
 
 class ModuleEngine:
@@ -31,10 +31,12 @@ class ModuleEngine:
         self.params = [p for _, p in self.module.named_parameters()]
 
     # -- optimizer state over trainable parameters only ------------------
-    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float):
+    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float,
+                       mu: float = 0.0):
         pp = self.packer.n_train_params
         st = {"kind": kind, "lr": torch.full((n_rows,), lr,
-                                             device=self.device), "wd": wd}
+                                             device=self.device), "wd": wd,
+              "mu": check_mu(mu)}
         if kind == "adam":
             st["m"] = torch.zeros(n_rows, pp, device=self.device)
             st["v"] = torch.zeros(n_rows, pp, device=self.device)
@@ -59,9 +61,14 @@ class ModuleEngine:
             p.copy_(vec[i:i + p.numel()].reshape(p.shape))
             i += p.numel()
 
-    def _step(self, opt: Dict, row: int, grads: torch.Tensor) -> None:
+    def _step(self, opt: Dict, row: int, grads: torch.Tensor,
+              anchor: Optional[torch.Tensor] = None) -> None:
         pvec = self._pvec()
         lr = float(opt["lr"][row])
+        mu = check_mu(opt.get("mu", 0.0))
+        if mu != 0.0:
+            # FedProx pull towards the trainable slice the round began from
+            grads = grads + mu * (pvec - anchor)
         if opt["kind"] == "sgd":
             pvec -= lr * grads
         else:
@@ -87,6 +94,8 @@ class ModuleEngine:
         for gi, row in enumerate(plan.rows):
             m_idx = int(row) % n_models
             self.packer.load_into(mod, global_params[m_idx])
+            anchor = (self._pvec() if check_mu(opt.get("mu", 0.0)) != 0.0
+                      else None)
             E = plan.step_off.shape[1]
             for e in range(E):
                 n = int(plan.step_len[gi, e])
@@ -102,7 +111,7 @@ class ModuleEngine:
                 with torch.enable_grad():
                     loss = F.cross_entropy(mod(x), y)
                     loss.backward()
-                self._step(opt, int(row), self._gvec())
+                self._step(opt, int(row), self._gvec(), anchor)
             self.packer.dump_from(mod, replicas[int(row)])
 
     @torch.no_grad()

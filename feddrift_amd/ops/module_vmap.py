@@ -31,7 +31,7 @@ from torch import nn
 from torch.func import functional_call, grad, vmap
 
 from ..models.generic_packer import ModulePacker
-from .mlp_torch import _apply_update
+from .mlp_torch import _apply_update, check_mu
 
 _BN_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -108,12 +108,13 @@ class VmapEngine:
             i += n
         return pv, bv
 
-    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float):
+    def make_opt_state(self, kind: str, n_rows: int, lr: float, wd: float,
+                       mu: float = 0.0):
         # optimizer state covers trainable parameters only (like the
         # sequential engine; buffers are not optimizer targets)
         from .mlp_torch import make_opt_state
         return make_opt_state(kind, n_rows, self.packer.n_train_params,
-                              lr, wd, self.device)
+                              lr, wd, self.device, mu=mu)
 
     # activation memory bound: vmapped conv activations scale with
     # pairs x batch; chunk the pair dimension (pairs are independent, so
@@ -158,6 +159,12 @@ class VmapEngine:
         else:
             st = {}
         lr = opt["lr"][rows]
+        # FedProx anchor: the trainable slice of each pair's global row
+        mu = check_mu(opt.get("mu", 0.0))
+        anchor = None
+        if mu != 0.0:
+            anchor = (work[:, self.param_idx] if self.has_buffers
+                      else work.clone())
         E = step_off.shape[1]
         for e in range(E):
             off = step_off[:, e]
@@ -191,6 +198,8 @@ class VmapEngine:
                 wp = work[:, self.param_idx]
             else:
                 wp = work
+            if mu != 0.0:
+                gflat = gflat + mu * (wp - anchor)
             sel = ln > 0
             if bool(sel.all()):
                 _apply_update(opt["kind"], lr, opt.get("wd", 0.0), st,

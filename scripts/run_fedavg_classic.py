@@ -54,6 +54,8 @@ def main():
     p.add_argument("--robust_norm_bound", type=float, default=0.0)
     p.add_argument("--robust_noise", type=float, default=0.0)
     p.add_argument("--robust_fused", type=int, default=0)
+    p.add_argument("--fedprox_mu", type=float, default=0.0,
+                   help="FedProx proximal coefficient (0 = plain FedAvg)")
     p.add_argument("--seed", type=int, default=0)
     a = p.parse_args()
 
@@ -86,6 +88,7 @@ def main():
                  robust_norm_bound=a.robust_norm_bound,
                  robust_noise=a.robust_noise,
                  robust_fused=a.robust_fused,
+                 fedprox_mu=a.fedprox_mu,
                  log_dir="/tmp/fedavg_classic")
     os.makedirs(cfg.log_dir, exist_ok=True)
     logger = MetricLogger(cfg.log_dir, enabled=comm.is_root, to_file=False)
