@@ -364,7 +364,10 @@ class CnnHipEngine:
                    masks: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Batched weighted ensemble vote over many tasks: per model, one
         probability-dump sweep; votes accumulate as batched torch ops.
-        weights: [M] or [n_tasks, M]. Returns [2, n_tasks] correct/total."""
+        weights: [M] or [n_tasks, M]. Returns [2, n_tasks] correct/total.
+        hard adds w to the argmax class of the model output, soft adds
+        w * softmax(model output); ties go to the lowest class, a vote row
+        of zeros to class 0 (specification: tests/vote_cases.py)."""
         dev = self.device
         self._x_arena, self._y_arena = x_arena, y_arena
         M = params.shape[0]
@@ -377,6 +380,15 @@ class CnnHipEngine:
                   if float(weights[:, m].abs().max() if per_task
                            else weights[m].abs()) > 0]
         if not active:
+            # no sweep: every vote row is zero and predicts class 0
+            # (np.argmax of zeros in the reference), the samples still count
+            slot = torch.cumsum(win_len, 0) - win_len
+            within = (torch.arange(int(win_len.sum()), device=dev)
+                      - slot.repeat_interleave(win_len))
+            y = y_arena[win_off.repeat_interleave(win_len) + within]
+            out[0].scatter_add_(0, task_id.repeat_interleave(win_len),
+                                (y == 0).double())
+            out[1].scatter_add_(0, task_id, win_len.double())
             return out
         slots_total = int(win_len.sum())
         votes = torch.zeros(slots_total, self.O, device=dev)
@@ -398,7 +410,9 @@ class CnnHipEngine:
                     contrib = torch.zeros_like(probs)
                     contrib.scatter_(1, probs.argmax(1, keepdim=True), 1.0)
                 else:
-                    contrib = probs
+                    # the reference's soft vote is softmax(model(x)), and
+                    # the model output (the dump) already is a softmax
+                    contrib = torch.softmax(probs, dim=1)
                 if per_task:
                     wslice = wv[stid, _m]
                 else:

@@ -171,7 +171,6 @@ class ModuleEngine:
                 continue
             x = x_arena[off:off + ln]
             y = y_arena[off:off + ln]
-            votes = torch.zeros(ln, dtype=torch.float32, device=self.device)
             votes = None
             for m in range(M):
                 wgt = float(weights[m])
@@ -181,16 +180,18 @@ class ModuleEngine:
                 xm = x * masks[m] if masks is not None else x
                 logits = mod(xm)
                 if votes is None:
-                    votes = torch.zeros(ln, logits.shape[-1],
-                                        device=self.device)
+                    votes = torch.zeros_like(logits)
                 if mode == "hard":
                     votes.scatter_add_(
                         1, logits.argmax(-1, keepdim=True),
-                        torch.full((ln, 1), wgt, device=self.device))
+                        torch.full_like(logits[:, :1], wgt))
                 else:
                     votes += wgt * torch.softmax(logits, -1)
             if votes is not None:
                 correct += float((votes.argmax(-1) == y).sum())
+            else:
+                # no active model: the all-zero vote row predicts class 0
+                correct += float((y == 0).sum())
             total += float(ln)
         return correct, total
 

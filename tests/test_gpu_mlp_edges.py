@@ -28,6 +28,7 @@ if not torch.cuda.is_available():          # pragma: no cover
     pytest.skip("GPU only", allow_module_level=True)
 
 import gpu_variant_cases as vc  # noqa: E402
+import vote_cases as vo  # noqa: E402
 from feddrift_amd.models.packed import spec_for  # noqa: E402
 from feddrift_amd.ops import mlp_hip, mlp_torch  # noqa: E402
 
@@ -298,3 +299,44 @@ def test_vote_per_task_weights_with_masks(kind, d, o, mode):
     torch.cuda.synchronize()
     assert torch.equal(got[1], ref[1])
     assert ((got[0] - ref[0]).abs() <= near_t).all(), (got[0], ref[0])
+
+    # The labels above are random, so a wrong prediction moves a count with
+    # probability about 2 / O only, and rand + 0.1 weights never tie. Again
+    # on windows that do not overlap, against tests/vote_cases.py: with the
+    # labels the float64 specification itself predicts (every slot the
+    # kernel gets wrong is one missing count), and, hard mode, with unit
+    # weights, where mlp_vote_kernel's strict `>` has to send the exactly
+    # tied votes to the lowest class.
+    tid2, off2, ln2 = wins2 = _disjoint_windows(g)
+    pos, task_of = vo.slot_index(wins2)
+    outs = vo.mlp_outputs(spec, params, x, pos, masks)
+    runs = [("per-task", weights, None)]
+    if mode == "hard":
+        ones = torch.ones(M)
+        ones[3] = 0.0
+        runs.append(("ones", ones, vo.MIN_TIE_SHARE_MLP))
+    for name, w, min_ties in runs:
+        def run(yy):
+            out = mlp_hip.ens_vote_multi(
+                spec, dv(params), dv(w), dv(x), dv(yy), dv(tid2), dv(off2),
+                dv(ln2), T, mode=mode, masks=dv(masks))
+            torch.cuda.synchronize()
+            return out
+        vo.check_vote(f"mlp vote {kind}({d},{o}) {mode} {name}", run, outs,
+                      w, task_of, pos, y, T, mode, out_gap=vc.NEAR_TIE_MLP,
+                      soft_gap=vc.NEAR_TIE_MLP, min_tie_share=min_ties)
+
+
+def _disjoint_windows(g):
+    """Ten windows of the EVAL_LENS lengths into 5 tasks, laid out one after
+    another in shuffled order with random gaps."""
+    ln = torch.tensor(EVAL_LENS + (65, 257, 1))
+    off = torch.zeros(len(ln), dtype=torch.int64)
+    at = 0
+    for w in torch.randperm(len(ln), generator=g).tolist():
+        at += int(torch.randint(0, 50, (1,), generator=g))
+        off[w] = at
+        at += int(ln[w])
+    assert at <= vc.MLP_N
+    task_id = torch.arange(len(ln)) % T
+    return task_id[torch.randperm(len(ln), generator=g)], off, ln
