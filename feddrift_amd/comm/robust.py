@@ -220,6 +220,118 @@ def order_stat_aggregate(replicas, rows, model_of, weights, K: int,
     return n_out, k_out
 
 
+# ---------------------------------------------------------------------------
+# robust_agg = multi_krum: the SPECIFICATION of Krum / Multi-Krum (Blanchard
+# et al., NeurIPS 2017) in numpy float64. ops/hip/krum_kernels.hip follows
+# it. A whole upload is judged by its squared L2 distances to the other
+# uploads of its model, which catches what the coordinate-wise rules above
+# cannot: colluders that stay inside the honest range of every coordinate.
+# Unweighted over a model's participants, for the reason given above.
+#
+# The rule's limit: it leaves out n - s rows. If more rows than that are
+# non-finite, a non-finite row is selected and the output row is non-finite.
+# ---------------------------------------------------------------------------
+
+def krum_f(frac: float, n: int) -> int:
+    """Byzantine uploads assumed among n: floor(frac n), capped so that
+    Krum's condition n >= 2f + 3 holds wherever it can (f = 0 below 3)."""
+    n = int(n)
+    return min(int(np.floor(frac * n + 1e-9)), max((n - 3) // 2, 0))
+
+
+def krum_sqdist(values) -> np.ndarray:
+    """D[i, j] = sum_p (double(x_ip) - double(x_jp))^2 of values [n, P]:
+    direct differences (uploads are the global row plus a small update, and
+    the Gram form |x|^2 + |y|^2 - 2 x.y cancels exactly there). The diagonal
+    is 0; a non-finite result (a NaN or Inf coordinate) is +Inf."""
+    v = np.ascontiguousarray(values, dtype=np.float32).astype(np.float64)
+    n = v.shape[0]
+    D = np.empty((n, n), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            d = v - v[i]
+            D[i] = (d * d).sum(axis=1)
+    D[~np.isfinite(D)] = np.inf
+    D[np.arange(n), np.arange(n)] = 0.0
+    return D
+
+
+def krum_scores(D, f: int) -> np.ndarray:
+    """score_i = the sum of the q = max(n - f - 2, 1) smallest D[i, j],
+    j != i, added in ascending order; 0 for n = 1."""
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    if n == 1:
+        return np.zeros(1, dtype=np.float64)
+    q = max(n - int(f) - 2, 1)
+    off = D[~np.eye(n, dtype=bool)].reshape(n, n - 1)
+    with np.errstate(all="ignore"):
+        return np.cumsum(np.sort(off, axis=1)[:, :q], axis=1)[:, q - 1]
+
+
+def krum_select(scores, ids, s: int) -> np.ndarray:
+    """Positions of the s participants of lowest (score, id), in that
+    order. Exact score ties are structural (with q = 1 two mutually nearest
+    rows always tie, D being symmetric): `ids` decides them."""
+    scores = np.asarray(scores, dtype=np.float64)
+    ids = np.asarray(ids, dtype=np.int64)
+    return np.lexsort((ids, scores))[:int(s)]
+
+
+def krum_counts(n: int, frac: float, select: int):
+    """(f, q, s) of a model with n >= 1 participants: s = n - f rows are
+    kept (at most `select` of them when select > 0)."""
+    f = krum_f(frac, n)
+    q = max(n - f - 2, 1) if n >= 2 else 0
+    s = n - f if select == 0 else min(int(select), n - f)
+    return f, q, s
+
+
+def multi_krum_aggregate(replicas, rows, model_of, weights, ids, K: int,
+                         frac: float, select: int, out, dtype=np.float32):
+    """out[m] <- Multi-Krum over model m's participant rows (the listed
+    pairs with weight > 0; ids[i] is pair i's tie-break key), for every
+    model with a participant: s = 1 stores the selected row's bits (classic
+    Krum), otherwise the selected rows are added in selection order in
+    `dtype` and divided by s. Other rows of `out` and `replicas` keep every
+    bit. Returns (n [K], f [K], s [K], selected ids per model, scores per
+    model in the pairs' order)."""
+    bank = replicas.detach().numpy() if isinstance(replicas, torch.Tensor) \
+        else np.asarray(replicas)
+    dst = out.detach().numpy() if isinstance(out, torch.Tensor) else out
+    rows = np.asarray(rows, dtype=np.int64)
+    mo = np.asarray(model_of, dtype=np.int64)
+    ids = np.asarray(ids, dtype=np.int64)
+    sel = np.asarray(weights) > 0
+    dt = np.dtype(dtype).type
+    n_out = np.zeros(K, dtype=np.int64)
+    f_out = np.zeros(K, dtype=np.int64)
+    s_out = np.zeros(K, dtype=np.int64)
+    chosen = [np.zeros(0, dtype=np.int64) for _ in range(K)]
+    scores = [np.zeros(0, dtype=np.float64) for _ in range(K)]
+    for m in range(K):
+        pick = sel & (mo == m)
+        r = rows[pick]
+        n = len(r)
+        n_out[m] = n
+        if n == 0:
+            continue
+        f, _, s = krum_counts(n, frac, select)
+        f_out[m], s_out[m] = f, s
+        scores[m] = krum_scores(krum_sqdist(bank[r]), f)
+        pos = krum_select(scores[m], ids[pick], s)
+        chosen[m] = ids[pick][pos]
+        if s == 1:
+            dst[m] = bank[r[pos[0]]]
+            continue
+        with np.errstate(all="ignore"):
+            acc = bank[r[pos[0]]].astype(dt)
+            for i in pos[1:]:
+                acc = acc + bank[r[i]].astype(dt)
+            dst[m] = acc / dt(s)
+    return n_out, f_out, s_out, chosen, scores
+
+
 def new_server_state(kind: str) -> dict:
     if kind not in SERVER_KINDS:
         raise ValueError(f"server optimizer '{kind}' is not one of "

@@ -78,9 +78,16 @@ class Config:
     robust_agg: str = "mean"             # mean|trimmed_mean|median: the
                                          # per-coordinate statistic over a
                                          # model's uploads (unweighted for
-                                         # the two order statistics)
+                                         # the two order statistics);
+                                         # multi_krum: the mean of the
+                                         # uploads closest to the others
     robust_trim_frac: float = 0.1        # trimmed_mean: share dropped at
                                          # either end, in [0, 0.5)
+    robust_krum_frac: float = 0.2        # multi_krum: share of a model's
+                                         # uploads assumed Byzantine, [0, 0.5)
+    robust_krum_select: int = 0          # multi_krum: uploads kept, 0 = all
+                                         # but the assumed Byzantine ones;
+                                         # 1 = classic Krum
     # FedOpt server optimizer ('avg' = plain FedAvg replacement)
     server_optimizer: str = "avg"
     server_lr: float = 1.0
@@ -104,12 +111,22 @@ class Config:
         if self.robust_fused not in (0, 1):
             raise ValueError("robust_fused must be 0 or 1, got "
                              f"{self.robust_fused}")
-        if self.robust_agg not in ("mean", "trimmed_mean", "median"):
+        if self.robust_agg not in ("mean", "trimmed_mean", "median",
+                                   "multi_krum"):
+            hint = " (classic Krum is robust_agg=multi_krum with " \
+                "robust_krum_select=1)" if self.robust_agg == "krum" else ""
             raise ValueError("robust_agg must be one of mean, trimmed_mean, "
-                             f"median, got '{self.robust_agg}'")
+                             f"median, multi_krum, got '{self.robust_agg}'"
+                             f"{hint}")
         if not 0.0 <= self.robust_trim_frac < 0.5:
             raise ValueError("robust_trim_frac must lie in [0, 0.5), got "
                              f"{self.robust_trim_frac}")
+        if not 0.0 <= self.robust_krum_frac < 0.5:
+            raise ValueError("robust_krum_frac must lie in [0, 0.5), got "
+                             f"{self.robust_krum_frac}")
+        if self.robust_krum_select < 0:
+            raise ValueError("robust_krum_select must be >= 0, got "
+                             f"{self.robust_krum_select}")
         if self.robust_agg != "mean" and self.secure_agg != 0:
             raise ValueError(
                 f"robust_agg='{self.robust_agg}' cannot run with secure_agg="

@@ -739,20 +739,33 @@ class FLJob:
 
     def _order_stat_partial(self, plan: TrainPlan,
                             partial: torch.Tensor) -> torch.Tensor:
-        """robust_agg = trimmed_mean | median: partial[m, :P] <- the
-        coordinate-wise statistic over model m's participants (the trained
-        pairs with a positive weight, of all ranks), partial[m, P] <- 1 for
-        a model with participants and 0 otherwise. At world size 1 the
+        """robust_agg = trimmed_mean | median | multi_krum: partial[m, :P]
+        <- the statistic over model m's participants (the trained pairs
+        with a positive weight, of all ranks), partial[m, P] <- 1 for a
+        model with participants and 0 otherwise. At world size 1 the
         kernel reads the replica bank through the plan's row list; above,
         every rank gathers all participant rows and computes the same
-        result from the same buffer. Returns the true per-model sum of
+        result from the same buffer. Multi-Krum breaks score ties by the
+        global worker id, which travels with the rows, so its selection is
+        the same at every world size. Returns the true per-model sum of
         weights over all ranks."""
-        from ..ops import orderstat_hip
+        from ..ops import krum_hip, orderstat_hip
         K, P = self.n_models, self.n_params
         cfg = self.cfg
         dev = self.device
+        krum = cfg.robust_agg == "multi_krum"
+
+        def make(rows, models, w, ids):
+            if krum:
+                return krum_hip.KrumPlan(
+                    rows, models, w, K, cfg.robust_krum_frac,
+                    cfg.robust_krum_select, ids)
+            return orderstat_hip.OrderStatPlan(
+                rows, models, w, K, cfg.robust_agg, cfg.robust_trim_frac)
+
         tmpl = plan.template
-        hit = getattr(tmpl, "_orderstat", None) if tmpl is not None else None
+        slot = "_krum" if krum else "_orderstat"
+        hit = getattr(tmpl, slot, None) if tmpl is not None else None
         if hit is not None and hit[0] is plan.sample_num:
             op, sum_w = hit[1], hit[2]
         else:
@@ -761,35 +774,52 @@ class FLJob:
             sn = np.asarray(plan.sample_num)
             w = sn[plan.rows // K, mo] if plan.rows.size else \
                 np.zeros(0, np.float32)
-            op = orderstat_hip.OrderStatPlan(
-                plan.rows, mo, w, K, cfg.robust_agg, cfg.robust_trim_frac)
+            own = np.asarray(self.owned_workers, dtype=np.int64)
+            op = make(plan.rows, mo, w, own[plan.rows // K])
             sum_w = torch.as_tensor(sn, dtype=torch.float32, device=dev) \
                 .reshape(-1, K).sum(dim=0)
             if tmpl is not None:
-                tmpl._orderstat = (plan.sample_num, op, sum_w)
+                setattr(tmpl, slot, (plan.sample_num, op, sum_w))
         bank = self.replicas
         if self.comm.distributed:
             sum_w = self.comm.all_reduce_(sum_w.clone())
             mine = torch.as_tensor(op.rows, device=dev)
             buf, counts = self.comm.all_gather_rows(self.replicas[mine])
-            ids, _ = self.comm.all_gather_rows(
-                torch.as_tensor(op.models, device=dev).unsqueeze(1))
+            cols = [torch.as_tensor(op.models, device=dev)]
+            if krum:
+                cols.append(torch.as_tensor(op.ids, device=dev))
+            ids, _ = self.comm.all_gather_rows(torch.stack(cols, dim=1))
             most = max(counts)
             at = np.concatenate([r * most + np.arange(c)
                                  for r, c in enumerate(counts)])
-            models = ids[:, 0].cpu().numpy()[at]
-            op = orderstat_hip.OrderStatPlan(
-                at, models, np.ones(len(at), np.float32), K,
-                cfg.robust_agg, cfg.robust_trim_frac)
+            ids = ids.cpu().numpy()[at]
+            op = make(at, ids[:, 0], np.ones(len(at), np.float32),
+                      ids[:, 1] if krum else None)
             bank = buf
         partial.zero_()
-        orderstat_hip.aggregate(bank, op, partial[:, :P])
+        if krum:
+            krum_hip.aggregate(bank, op, partial[:, :P])
+            self._krum_last = op
+        else:
+            orderstat_hip.aggregate(bank, op, partial[:, :P])
         if getattr(op, "_has", None) is None:
             op._has = torch.as_tensor((op.n > 0).astype(np.float32),
                                       device=dev)
         partial[:, P] = op._has
         self._partial_clean = False
         return sum_w
+
+    def krum_selection(self) -> List[np.ndarray]:
+        """robust_agg=multi_krum: per model, the global worker ids the last
+        aggregation kept, in (score, id) order (on a GPU: one
+        synchronisation and one copy, only here). Empty for every other
+        robust_agg and before the first aggregation."""
+        op = getattr(self, "_krum_last", None)
+        if op is None:
+            return [np.zeros(0, dtype=np.int64)
+                    for _ in range(self.n_models)]
+        from ..ops import krum_hip
+        return krum_hip.last_selection(op)
 
     def _apply_secure_masks(self, plan: TrainPlan,
                             partial: torch.Tensor) -> None:
