@@ -186,6 +186,11 @@ class FLJob:
             self.spec = None
             from ..ops.module_vmap import VmapEngine, vmap_compatible
             has_buffers = len(list(proto0.buffers())) > 0
+            if has_buffers and cfg.upload_compress != "none":
+                raise ValueError(
+                    f"upload_compress='{cfg.upload_compress}' supports the "
+                    f"models without buffers (lr, fnn, cnn); '{cfg.model}' "
+                    "carries BatchNorm running statistics")
             # CNN_DropOut on a GPU: the hand-written CDNA4 kernel engine
             # (ops/cnn_hip.py, ops/hip/cnn_kernels.hip) owns the hot path
             # end-to-end. Required on GPU devices unless explicitly
@@ -319,6 +324,24 @@ class FLJob:
             self._noise_ctr = 0
             self._clip_counts = robust_hip.new_counts(self.n_models,
                                                       self.device)
+            # the pass run with an infinite bound (upload_compress without
+            # a norm bound) counts here, so clip_stats() stays as it is
+            self._clip_unbounded = robust_hip.new_counts(self.n_models,
+                                                         self.device)
+        # upload_compress=topk: a pass over the trained rows between train
+        # and clip (ops/compress_hip.py); the residual bank is the pairs'
+        # error-feedback memory, owned by the replica row like the
+        # optimizer state
+        self._compress = cfg.upload_compress != "none"
+        self._residual: Optional[torch.Tensor] = None
+        if self._compress:
+            from ..comm.compress import keep_count
+            from ..ops import compress_hip
+            self._compress_k = keep_count(cfg.compress_ratio, P)
+            self._compress_counts = compress_hip.new_counts(self.n_models,
+                                                            self.device)
+            if cfg.compress_error_feedback == 1:
+                self._residual = torch.zeros_like(self.replicas)
         self.algo.init_iteration(self)
 
     # ------------------------------------------------------------------
@@ -492,6 +515,11 @@ class FLJob:
         # launch keeps its fused broadcast but drops the float partial
         # (an order statistic reads them too: robust_agg != "mean")
         ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
+        # upload_compress edits the rows after the launch, so the launch
+        # drops its fused partial as it does for fused_clip; the clip pass
+        # (robust_fused=1) or aggregate()'s unfused sums take its place
+        comp = self._compress
+        clip_pass = self._fused_clip_runs(ring)
         if self._partial is None or self._partial.shape[0] != K:
             self._partial = torch.zeros(K, P + 1, device=dev)
             self._totals = torch.zeros(K, device=dev)
@@ -512,6 +540,7 @@ class FLJob:
                                   self.opt, self.arena.x, self.arena.y,
                                   K, x_mask=plan.x_mask)
             self._partial_fused = False
+            self._compress_pass(plan)
             self._robust_clip(plan)
             return
         off_t, len_t = self._upload_steps(plan, dev)
@@ -536,10 +565,12 @@ class FLJob:
                 off_t, len_t, self.opt, x_mask=plan.x_mask,
                 in_params=self.global_params,
                 model_of=mo_t,
-                sample_w=None if ring or fused_clip else sw_t,
-                partial=None if ring or fused_clip else self._partial)
-            self._partial_fused = not ring
-            if fused_clip:
+                sample_w=None if ring or clip_pass or comp else sw_t,
+                partial=None if ring or clip_pass or comp
+                else self._partial)
+            self._partial_fused = not ring and (not comp or clip_pass)
+            self._compress_pass(plan)
+            if clip_pass:
                 self._robust_clip_fused(plan, ring)
         else:
             self.sync_replicas()
@@ -548,6 +579,7 @@ class FLJob:
                 self.spec, self.replicas, rows_t, self.arena.x, self.arena.y,
                 off_t, len_t, self.opt, x_mask=plan.x_mask)
             self._partial_fused = False
+            self._compress_pass(plan)
             self._robust_clip(plan)
 
     def _upload_steps(self, plan: TrainPlan, dev: torch.device):
@@ -584,16 +616,20 @@ class FLJob:
         """Optional defense: clip client updates to an L2 ball before they
         enter the aggregation (fedavg_robust equivalent,
         fedml_core robustness/robust_aggregation.py:38)."""
-        if self.cfg.robust_norm_bound <= 0 or plan.rows.size == 0:
+        if plan.rows.size == 0:
             return
         if self._robust_fused:
             ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
+            if not self._fused_clip_runs(ring):
+                return
             if not ring:
                 if not getattr(self, "_partial_clean", False):
                     self._partial.zero_()
                 self._partial_clean = False
                 self._partial_fused = True
             self._robust_clip_fused(plan, ring)
+            return
+        if self.cfg.robust_norm_bound <= 0:
             return
         from ..comm.robust import robustify_replicas
         rows_t = torch.as_tensor(plan.rows, dtype=torch.int64,
@@ -620,10 +656,56 @@ class FLJob:
                 plan.rows, mo, plan.sample_num[plan.rows // K, mo], K)
             if tmpl is not None:
                 tmpl._robust = (plan.sample_num, cp)
+        bounded = self.cfg.robust_norm_bound > 0
         robust_hip.clip_accumulate(
             self.replicas, cp, self.global_params,
-            self.cfg.robust_norm_bound, None if ring else self._partial,
-            self._clip_counts)
+            self.cfg.robust_norm_bound if bounded else float("inf"),
+            None if ring else self._partial,
+            self._clip_counts if bounded else self._clip_unbounded)
+
+    def _fused_clip_runs(self, ring: bool) -> bool:
+        """robust_fused=1 runs its clip pass for a norm bound, and for the
+        weighted sums of compressed rows: without a bound the pass takes an
+        infinite one, under which no row's factor is below 1, so every row
+        keeps its bits."""
+        return self._robust_fused and (
+            self.cfg.robust_norm_bound > 0 or (self._compress and not ring))
+
+    def _compress_pass(self, plan: TrainPlan) -> None:
+        """upload_compress=topk: one pass over the trained rows, whatever
+        their aggregation weight (ops/compress_hip.py). The pair list is
+        cached on the plan template."""
+        if not self._compress or plan.rows.size == 0:
+            return
+        from ..ops import compress_hip
+        tmpl = plan.template
+        cp = getattr(tmpl, "_compress", None) if tmpl is not None else None
+        if cp is None:
+            cp = compress_hip.CompressPlan(
+                plan.rows, plan.rows % self.n_models, self.n_models)
+            if tmpl is not None:
+                tmpl._compress = cp
+        compress_hip.topk(self.replicas, cp, self.global_params,
+                          self._residual, self._compress_k,
+                          self._compress_counts)
+
+    def compress_stats(self) -> np.ndarray:
+        """[K, 2] per-model (sent, total) coordinate counts of the trained
+        rows since the last call, summed across ranks (one small
+        all_reduce); resets them. Zeros when upload_compress is none."""
+        if not self._compress:
+            return np.zeros((self.n_models, 2), dtype=np.int64)
+        tot = self._compress_counts.to(torch.float64)
+        self.comm.all_reduce_(tot)
+        self._compress_counts.zero_()
+        return tot.cpu().numpy().astype(np.int64)
+
+    def _zero_residual(self, m: int) -> None:
+        """Model m's row was overwritten: the residuals held against the
+        old model must not be uploaded."""
+        if self._residual is not None:
+            self._residual.view(len(self.owned_workers), self.n_models,
+                                self.n_params)[:, m].zero_()
 
     def clip_stats(self) -> np.ndarray:
         """[K, 2] per-model (clipped, seen) pair counts since the last
@@ -944,9 +1026,11 @@ class FLJob:
 
     def reinit_model(self, m: int) -> None:
         self.global_params[m] = self.init_flat
+        self._zero_residual(m)
 
     def copy_model(self, dst: int, src: int) -> None:
         self.global_params[dst] = self.global_params[src]
+        self._zero_residual(dst)
 
     def randomize_models_unseeded(self) -> None:
         """reference 'hard' iter-0 quirk: reset_parameters() WITHOUT
@@ -970,6 +1054,7 @@ class FLJob:
                     layer.reset_parameters()
             self.global_params[m] = self.packer.flatten(
                 proto.state_dict()).to(self.device)
+            self._zero_residual(m)
 
     def train_acc_matrix_rows(self, model_rows: List[int]) -> np.ndarray:
         """[len(rows), C] acc of each global model row on each client's
@@ -1116,6 +1201,14 @@ class FLJob:
                     if stats[m, 1] > 0:
                         self.logger.log(
                             {f"Robust/ClipFrac-m{m}":
+                             stats[m, 0] / stats[m, 1]}, round_idx)
+        if self._compress:
+            stats = self.compress_stats()      # all ranks: it all_reduces
+            if self.comm.is_root:
+                for m in range(self.n_models):
+                    if stats[m, 1] > 0:
+                        self.logger.log(
+                            {f"Compress/SentFrac-m{m}":
                              stats[m, 0] / stats[m, 1]}, round_idx)
 
     # ------------------------------------------------------------------

@@ -18,7 +18,9 @@ SRC_ROBUST = os.path.join(_DIR, "hip", "robust_kernels.hip")
 # the one source list both build functions compile
 SRC_ORDERSTAT = os.path.join(_DIR, "hip", "orderstat_kernels.hip")
 SRC_KRUM = os.path.join(_DIR, "hip", "krum_kernels.hip")
-SOURCES = [SRC, SRC_CNN, SRC_SECAGG, SRC_ROBUST, SRC_ORDERSTAT, SRC_KRUM]
+SRC_COMPRESS = os.path.join(_DIR, "hip", "compress_kernels.hip")
+SOURCES = [SRC, SRC_CNN, SRC_SECAGG, SRC_ROBUST, SRC_ORDERSTAT, SRC_KRUM,
+           SRC_COMPRESS]
 BUILD_DIR = os.path.join(_DIR, "hip", "_build")
 MODULE_NAME = "feddrift_hip"
 

@@ -1163,6 +1163,7 @@ void register_secagg(pybind11::module_& mod);  // secagg_kernels.hip
 void register_robust(pybind11::module_& mod);  // robust_kernels.hip
 void register_orderstat(pybind11::module_& mod);  // orderstat_kernels.hip
 void register_krum(pybind11::module_& mod);  // krum_kernels.hip
+void register_compress(pybind11::module_& mod);  // compress_kernels.hip
 
 torch::Tensor ens_vote_multi_hip(
     torch::Tensor params, torch::Tensor weights, torch::Tensor x,
@@ -1250,4 +1251,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_robust(mod);
   register_orderstat(mod);
   register_krum(mod);
+  register_compress(mod);
 }
