@@ -28,8 +28,8 @@ from __future__ import annotations
 
 import os
 import pickle
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass, field
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -56,6 +56,16 @@ class PlanTemplate:
     pool_size: np.ndarray    # [G]
     pool_off: np.ndarray     # [sum pools]
     pool_len: np.ndarray     # [sum pools]
+    # per-template constants: slot -> (the sample_num built from, value)
+    cache: dict = field(default_factory=dict, repr=False, compare=False)
+
+    def slot(self, name, sample_num: np.ndarray, build):
+        """The cached value of slot `name`, rebuilt when `sample_num` is not
+        the array it was built from."""
+        hit = self.cache.get(name)
+        if hit is None or hit[0] is not sample_num:
+            hit = self.cache[name] = (sample_num, build())
+        return hit[1]
 
     def draw(self, rng: np.random.Generator, epochs: int) -> "TrainPlan":
         G = len(self.rows)
@@ -67,14 +77,10 @@ class PlanTemplate:
         # allocations cost more than the draw itself.  Generator.random
         # with `out=` consumes the identical bit stream as random(size),
         # so cached-buffer draws are bit-equal to the uncached path.
-        sc = getattr(self, "_scratch", None)
-        if sc is None or sc[0].shape != (G, epochs):
-            sc = (np.empty((G, epochs), np.float64),
-                  np.empty((G, epochs), np.int64),
-                  np.empty((G, epochs), np.int64),
-                  np.empty((G, epochs), np.int64))
-            self._scratch = sc
-        u, idx, off_o, len_o = sc
+        u, idx, off_o, len_o = self.slot(
+            ("scratch", epochs), self.sample_num,
+            lambda: tuple(np.empty((G, epochs), t) for t in
+                          (np.float64, np.int64, np.int64, np.int64)))
         rng.random(out=u)
         np.multiply(u, self.pool_size[:, None], out=u)
         idx[:] = u                          # float -> int64 truncation
@@ -147,6 +153,16 @@ class TaskList:
                 self.ln.append(ln)
                 o += ln
                 l -= ln
+
+
+class Route(NamedTuple):
+    """One round's path between train and aggregate (FLJob._route)."""
+    launch: str     # "staged" by the launch itself | "synced" first | "module"
+    compress: bool  # the upload_compress pass runs after the launch
+    clip: str       # "fused" (_robust_clip_fused) | "eager" | "none"
+    fill: str       # who fills the partial: the "train" launch | the fused
+                    # "clip" | aggregate()'s "einsum" | nobody: it reads "rows"
+    zero: bool      # the partial is zeroed before the launch
 
 
 class FLJob:
@@ -233,6 +249,8 @@ class FLJob:
 
         self.n_params = self.packer.n_params if self.is_module_path \
             else self.spec.n_params
+        self._hip_mlp = not self.is_module_path and \
+            self.backend is not ops.mlp_torch
 
         from . import algorithms
         self.algo = algorithms.make(cfg)
@@ -291,8 +309,13 @@ class FLJob:
 
         self._eval_cache: Dict = {}
         self._eval_fast: Optional[tuple] = None
-        self._partial: Optional[torch.Tensor] = None
+        self._partial: Optional[torch.Tensor] = None   # [K, P+1], _route()
+        self._totals: Optional[torch.Tensor] = None
         self._partial_fused = False
+        self._partial_clean = False          # drained by the apply kernel
+        self._noise_gen: Optional[torch.Generator] = None   # robust_fused=0
+        self._server_opt = None              # robust_fused=0, first step
+        self._krum_last = None               # the last round's KrumPlan
         # secure_agg=2 (ring arithmetic): intra-rank pairs cancel inside a
         # rank's contribution, so they are skipped unless this switch is
         # cleared (a world-1 run then draws every mask; tests and the
@@ -370,20 +393,22 @@ class FLJob:
 
     def run_eval_dev(self, params: torch.Tensor, tl: TaskList,
                      want_mse: bool = False,
-                     idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     idx: Optional[torch.Tensor] = None,
+                     arena: Optional[tuple] = None) -> torch.Tensor:
         """Batched eval sweep; returns a stacked DEVICE tensor
         [correct; total; loss (; mse)] x n_tasks (float64) — callers
-        all_reduce it and download once."""
+        all_reduce it and download once. `arena`: an (x, y) pair to sweep
+        instead of the job's own."""
         if idx is None:
             idx = self.eval_tensors(tl)
+        x, y = arena or (self.arena.x, self.arena.y)
         if self.is_module_path:
             return self.mod_engine.eval_tasks_stacked(
                 params, idx[0], idx[1], idx[2], idx[3], tl.n_tasks,
-                want_mse=want_mse, x_arena=self.arena.x,
-                y_arena=self.arena.y)
+                want_mse=want_mse, x_arena=x, y_arena=y)
         return self.backend.eval_tasks_stacked(
-            self.spec, params, self.arena.x, self.arena.y,
-            idx[0], idx[1], idx[2], idx[3], tl.n_tasks, want_mse=want_mse)
+            self.spec, params, x, y, idx[0], idx[1], idx[2], idx[3],
+            tl.n_tasks, want_mse=want_mse)
 
     def run_eval(self, params: torch.Tensor, tl: TaskList,
                  want_mse: bool = False):
@@ -477,15 +502,7 @@ class FLJob:
         else:
             x_t = torch.zeros(1, self.dataset.feature_num, device=dev)
             y_t = torch.zeros(1, dtype=torch.int64, device=dev)
-        idx = self.eval_tensors(tl)
-        if self.is_module_path:
-            res = self.mod_engine.eval_tasks_stacked(
-                params, idx[0], idx[1], idx[2], idx[3], tl.n_tasks,
-                x_arena=x_t, y_arena=y_t)
-        else:
-            res = self.backend.eval_tasks_stacked(
-                self.spec, params, x_t, y_t, idx[0], idx[1], idx[2],
-                idx[3], tl.n_tasks)
+        res = self.run_eval_dev(params, tl, arena=(x_t, y_t))
         self.comm.all_reduce_(res)
         cv = res.cpu().numpy()
         correct = np.zeros((M, C))
@@ -495,92 +512,148 @@ class FLJob:
             total[m, c] = cv[1][tid]
         return correct, total
 
+    def cached(self, plan: TrainPlan, slot, build):
+        """build()'s value, kept on the plan's template under `slot` while
+        plans carry the same sample_num array; built anew without one."""
+        if plan.template is None:
+            return build()
+        return plan.template.slot(slot, plan.sample_num, build)
+
+    def _pairs(self, plan: TrainPlan):
+        """The trained pairs as (replica rows, models, aggregation weights,
+        global worker ids), each [G]."""
+        def build():
+            wi, mo = plan.rows // self.n_models, plan.rows % self.n_models
+            w = np.asarray(plan.sample_num)[wi, mo] if plan.rows.size \
+                else np.zeros(0, np.float32)
+            own = np.asarray(self.owned_workers, dtype=np.int64)
+            return plan.rows, mo, w, own[wi]
+        return self.cached(plan, "pairs", build)
+
+    def _route(self, empty: bool = False) -> Route:
+        """The round's path between train and aggregate, from the job's
+        options (per train() call: _compress may be switched between calls).
+        launch: "module" for a module model; "staged" for the MLP on the HIP
+        backend, unless a bound without robust_fused wants the replicas
+        synced for its eager clip; else (that, or the torch backend)
+        "synced". rows = the aggregation reads the replica rows itself
+        (secure_agg=2 or an order statistic); comp = upload_compress, whose
+        pass runs wherever it is set, before the clip; `-` = either.
+
+          bound fused rows comp | clip    fill
+          no    -     no   no   | none    train if staged, else einsum
+          no    0     no   yes  | none    einsum
+          no    1     no   yes  | fused*  clip
+          yes   0     no   -    | eager   einsum
+          yes   1     no   -    | fused   clip
+          no    -     yes  -    | none    rows
+          yes   0     yes  -    | eager   rows
+          yes   1     yes  -    | fused   rows
+          empty plan: no pass runs ("synced" still syncs), whatever comp;
+          -     -     no   -    | none    train if staged, else einsum
+          -     -     yes  -    | none    rows
+
+        * with an infinite bound (_robust_clip_fused), for the sums alone.
+        An empty plan's fill "train" is the zeroed partial, left as it is.
+        The partial is zeroed before the launch when the clip fills it, and
+        for a staged launch unless rows."""
+        cfg, fused = self.cfg, self._robust_fused
+        bound = cfg.robust_norm_bound > 0
+        comp = self._compress and not empty
+        rows = cfg.secure_agg == 2 or cfg.robust_agg != "mean"
+        staged = self._hip_mlp and (fused or not bound)
+        launch = "staged" if staged else \
+            "module" if self.is_module_path else "synced"
+        if empty:
+            clip = "none"
+        elif fused:
+            clip = "fused" if bound or (comp and not rows) else "none"
+        else:
+            clip = "eager" if bound else "none"
+        if rows:
+            fill = "rows"
+        elif clip == "fused":
+            fill = "clip"
+        elif staged and not comp:
+            fill = "train"      # an empty plan: the zeroed sums stand
+        else:
+            fill = "einsum"
+        return Route(launch, comp, clip, fill,
+                     fill == "clip" or (staged and not rows))
+
+    def _zero_partial(self) -> None:
+        """Zero the partial for a round that accumulates into it. The apply
+        kernels drain it on their way out: steady-state rounds skip this."""
+        if not self._partial_clean:
+            self._partial.zero_()
+        self._partial_clean = False
+
     def train(self, plan: TrainPlan) -> None:
         """All local training of this round in ONE fused launch. On the HIP
         path the kernel also (a) stages each pair's initial weights straight
         from the global model row (fusing the server->client broadcast) and
         (b) accumulates the weighted aggregation partial sums on its way out
         — so the whole round's compute is train-kernel + all_reduce +
-        apply-kernel."""
+        apply-kernel. _route() decides the path, options' passes included."""
         K, P = self.n_models, self.n_params
         dev = self.device
-        robust = self.cfg.robust_norm_bound > 0
-        # robust_fused=1 keeps the fused launch and clips in a pass of its
-        # own (_robust_clip_fused) between train and aggregate
-        fused_clip = robust and self._robust_fused
-        hip = (not self.is_module_path) and self.backend is not ops.mlp_torch \
-            and (fused_clip or not robust)   # clipping happens between
-                                             # train and aggregate
-        # ring-arithmetic secure aggregation reads the replicas itself: the
-        # launch keeps its fused broadcast but drops the float partial
-        # (an order statistic reads them too: robust_agg != "mean")
-        ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
-        # upload_compress edits the rows after the launch, so the launch
-        # drops its fused partial as it does for fused_clip; the clip pass
-        # (robust_fused=1) or aggregate()'s unfused sums take its place
-        comp = self._compress
-        clip_pass = self._fused_clip_runs(ring)
+        empty = plan.rows.size == 0
+        route = self._route(empty)
         if self._partial is None or self._partial.shape[0] != K:
             self._partial = torch.zeros(K, P + 1, device=dev)
             self._totals = torch.zeros(K, device=dev)
             self._partial_clean = True
-        if hip and not ring:
-            # the apply kernel drains partial to zero on its way out, so
-            # steady-state rounds skip this fill entirely
-            if not getattr(self, "_partial_clean", False):
-                self._partial.zero_()
-            self._partial_clean = False
-        if plan.rows.size == 0:
-            self._partial_fused = hip and not ring
-            if not hip and not self.is_module_path:
-                self.sync_replicas()
+        self._partial_fused = route.fill in ("train", "clip")
+        if route.zero:
+            self._zero_partial()
+        if route.launch == "synced":
+            self.sync_replicas()
+        if empty:
             return
-        if self.is_module_path:
+        if route.launch == "module":
             self.mod_engine.train(self.global_params, self.replicas, plan,
                                   self.opt, self.arena.x, self.arena.y,
                                   K, x_mask=plan.x_mask)
-            self._partial_fused = False
-            self._compress_pass(plan)
-            self._robust_clip(plan)
-            return
-        off_t, len_t = self._upload_steps(plan, dev)
-        if hip:
-            # per-template constants (rows / model / aggregation weights)
-            # are uploaded once and reused every round
-            tmpl = plan.template
-            cache = getattr(tmpl, "_dev", None) if tmpl is not None else None
-            if cache is None:
-                wi = plan.rows // K
-                mo = (plan.rows % K).astype(np.int32)
-                sw = plan.sample_num[wi, plan.rows % K].astype(np.float32)
-                cache = (
-                    torch.as_tensor(plan.rows, dtype=torch.int64, device=dev),
-                    torch.as_tensor(mo, device=dev),
-                    torch.as_tensor(sw, device=dev))
-                if tmpl is not None:
-                    tmpl._dev = cache
-            rows_t, mo_t, sw_t = cache
+        elif route.launch == "staged":
+            off_t, len_t = self._upload_steps(plan, dev)
+            rows_t, mo_t, sw_t = self.cached(
+                plan, "train", lambda: self._train_constants(plan))
+            # the launch drops its sums when a later pass edits the rows
+            # or the aggregation reads them itself
+            acc = route.fill == "train"
             self.backend.train_fused(
                 self.spec, self.replicas, rows_t, self.arena.x, self.arena.y,
                 off_t, len_t, self.opt, x_mask=plan.x_mask,
-                in_params=self.global_params,
-                model_of=mo_t,
-                sample_w=None if ring or clip_pass or comp else sw_t,
-                partial=None if ring or clip_pass or comp
-                else self._partial)
-            self._partial_fused = not ring and (not comp or clip_pass)
-            self._compress_pass(plan)
-            if clip_pass:
-                self._robust_clip_fused(plan, ring)
+                in_params=self.global_params, model_of=mo_t,
+                sample_w=sw_t if acc else None,
+                partial=self._partial if acc else None)
         else:
-            self.sync_replicas()
+            off_t, len_t = self._upload_steps(plan, dev)
             rows_t = torch.as_tensor(plan.rows, dtype=torch.int64, device=dev)
             self.backend.train_fused(
                 self.spec, self.replicas, rows_t, self.arena.x, self.arena.y,
                 off_t, len_t, self.opt, x_mask=plan.x_mask)
-            self._partial_fused = False
+        # after train, whichever launch: upload_compress, then the clip
+        # (eager: the reference's fedavg_robust, fedml_core
+        # robustness/robust_aggregation.py:38)
+        if route.compress:
             self._compress_pass(plan)
-            self._robust_clip(plan)
+        if route.clip == "fused":
+            self._robust_clip_fused(plan, route.fill == "rows")
+        elif route.clip == "eager":
+            from ..comm.robust import robustify_replicas
+            t = lambda a: torch.as_tensor(a, dtype=torch.int64, device=dev)
+            robustify_replicas(
+                self.replicas, self.global_params, t(plan.rows),
+                t(plan.rows % K), self.cfg.robust_norm_bound)
+
+    def _train_constants(self, plan: TrainPlan):
+        """Per-template constants of the staged launch (rows / model /
+        aggregation weights): uploaded once and reused every round."""
+        rows, mo, w, _ = self._pairs(plan)
+        t = lambda a, dt: torch.as_tensor(np.asarray(a, dt),
+                                          device=self.device)
+        return t(rows, np.int64), t(mo, np.int32), t(w, np.float32)
 
     def _upload_steps(self, plan: TrainPlan, dev: torch.device):
         """Per-round upload of the [G, E] step windows. On GPU, a pageable
@@ -588,21 +661,18 @@ class FLJob:
         a per-template pinned double buffer turns both arrays into ONE
         non-blocking DMA (the buffer slot is event-guarded against reuse
         while a previous round's copy is still in flight)."""
-        tmpl = plan.template
-        if dev.type != "cuda" or tmpl is None:
-            return (torch.as_tensor(plan.step_off, dtype=torch.int64,
-                                    device=dev),
-                    torch.as_tensor(plan.step_len, dtype=torch.int64,
-                                    device=dev))
+        if dev.type != "cuda" or plan.template is None:
+            t = lambda a: torch.as_tensor(a, dtype=torch.int64, device=dev)
+            return t(plan.step_off), t(plan.step_len)
         G, E = plan.step_off.shape
-        st = getattr(tmpl, "_stage", None)
-        if st is None or st["pin"].shape[2:] != (G, E):
-            pin = torch.empty(2, 2, G, E, dtype=torch.int64,
-                              pin_memory=True)
-            tmpl._stage = st = {
+
+        def build():
+            pin = torch.empty(2, 2, G, E, dtype=torch.int64, pin_memory=True)
+            return {
                 "pin": pin, "np": pin.numpy(),
                 "buf": torch.empty(2, G, E, dtype=torch.int64, device=dev),
                 "ev": [torch.cuda.Event(), torch.cuda.Event()], "slot": 0}
+        st = self.cached(plan, ("stage", E), build)
         slot = st["slot"]
         st["slot"] = slot ^ 1
         st["ev"][slot].synchronize()
@@ -612,50 +682,16 @@ class FLJob:
         st["ev"][slot].record()
         return st["buf"][0], st["buf"][1]
 
-    def _robust_clip(self, plan: TrainPlan) -> None:
-        """Optional defense: clip client updates to an L2 ball before they
-        enter the aggregation (fedavg_robust equivalent,
-        fedml_core robustness/robust_aggregation.py:38)."""
-        if plan.rows.size == 0:
-            return
-        if self._robust_fused:
-            ring = self.cfg.secure_agg == 2 or self.cfg.robust_agg != "mean"
-            if not self._fused_clip_runs(ring):
-                return
-            if not ring:
-                if not getattr(self, "_partial_clean", False):
-                    self._partial.zero_()
-                self._partial_clean = False
-                self._partial_fused = True
-            self._robust_clip_fused(plan, ring)
-            return
-        if self.cfg.robust_norm_bound <= 0:
-            return
-        from ..comm.robust import robustify_replicas
-        rows_t = torch.as_tensor(plan.rows, dtype=torch.int64,
-                                 device=self.device)
-        mo = torch.as_tensor(plan.rows % self.n_models, device=self.device)
-        robustify_replicas(self.replicas, self.global_params, rows_t, mo,
-                           self.cfg.robust_norm_bound)
-
     def _robust_clip_fused(self, plan: TrainPlan, ring: bool) -> None:
         """robust_fused=1: one clip pass over the trained rows. It clips
         them in place and adds their weighted sums into the (zeroed)
         partial tensor; under secure_agg=2 or an order statistic (`ring`)
-        it only clips, and that path reads the replicas itself. The
-        pairs-by-model structure is cached on the plan template."""
+        it only clips, and that path reads the replicas itself. Without a
+        norm bound (the weighted sums of compressed rows) the pass takes an
+        infinite one, under which no row's factor is below 1."""
         from ..ops import robust_hip
-        K = self.n_models
-        tmpl = plan.template
-        hit = getattr(tmpl, "_robust", None) if tmpl is not None else None
-        if hit is not None and hit[0] is plan.sample_num:
-            cp = hit[1]
-        else:
-            mo = plan.rows % K
-            cp = robust_hip.ClipPlan(
-                plan.rows, mo, plan.sample_num[plan.rows // K, mo], K)
-            if tmpl is not None:
-                tmpl._robust = (plan.sample_num, cp)
+        cp = self.cached(plan, "clip", lambda: robust_hip.ClipPlan(
+            *self._pairs(plan)[:3], self.n_models))
         bounded = self.cfg.robust_norm_bound > 0
         robust_hip.clip_accumulate(
             self.replicas, cp, self.global_params,
@@ -663,42 +699,34 @@ class FLJob:
             None if ring else self._partial,
             self._clip_counts if bounded else self._clip_unbounded)
 
-    def _fused_clip_runs(self, ring: bool) -> bool:
-        """robust_fused=1 runs its clip pass for a norm bound, and for the
-        weighted sums of compressed rows: without a bound the pass takes an
-        infinite one, under which no row's factor is below 1, so every row
-        keeps its bits."""
-        return self._robust_fused and (
-            self.cfg.robust_norm_bound > 0 or (self._compress and not ring))
-
     def _compress_pass(self, plan: TrainPlan) -> None:
         """upload_compress=topk: one pass over the trained rows, whatever
-        their aggregation weight (ops/compress_hip.py). The pair list is
-        cached on the plan template."""
+        their aggregation weight (ops/compress_hip.py)."""
         if not self._compress or plan.rows.size == 0:
             return
         from ..ops import compress_hip
-        tmpl = plan.template
-        cp = getattr(tmpl, "_compress", None) if tmpl is not None else None
-        if cp is None:
-            cp = compress_hip.CompressPlan(
-                plan.rows, plan.rows % self.n_models, self.n_models)
-            if tmpl is not None:
-                tmpl._compress = cp
+        cp = self.cached(plan, "compress", lambda: compress_hip.CompressPlan(
+            *self._pairs(plan)[:2], self.n_models))
         compress_hip.topk(self.replicas, cp, self.global_params,
                           self._residual, self._compress_k,
                           self._compress_counts)
+
+    def _drain_counts(self, counts: Optional[torch.Tensor]) -> np.ndarray:
+        """[K, 2] int64: a per-model device counter summed across ranks
+        (one small all_reduce) and reset; zeros for None."""
+        if counts is None:
+            return np.zeros((self.n_models, 2), dtype=np.int64)
+        tot = counts.to(torch.float64)
+        self.comm.all_reduce_(tot)
+        counts.zero_()
+        return tot.cpu().numpy().astype(np.int64)
 
     def compress_stats(self) -> np.ndarray:
         """[K, 2] per-model (sent, total) coordinate counts of the trained
         rows since the last call, summed across ranks (one small
         all_reduce); resets them. Zeros when upload_compress is none."""
-        if not self._compress:
-            return np.zeros((self.n_models, 2), dtype=np.int64)
-        tot = self._compress_counts.to(torch.float64)
-        self.comm.all_reduce_(tot)
-        self._compress_counts.zero_()
-        return tot.cpu().numpy().astype(np.int64)
+        return self._drain_counts(
+            self._compress_counts if self._compress else None)
 
     def _zero_residual(self, m: int) -> None:
         """Model m's row was overwritten: the residuals held against the
@@ -711,12 +739,8 @@ class FLJob:
         """[K, 2] per-model (clipped, seen) pair counts since the last
         call, summed across ranks (one small all_reduce); resets them.
         Zeros unless robust_fused=1 with a norm bound."""
-        if not self._robust_fused:
-            return np.zeros((self.n_models, 2), dtype=np.int64)
-        tot = self._clip_counts.to(torch.float64)
-        self.comm.all_reduce_(tot)
-        self._clip_counts.zero_()
-        return tot.cpu().numpy().astype(np.int64)
+        return self._drain_counts(
+            self._clip_counts if self._robust_fused else None)
 
     def aggregate(self, plan: TrainPlan,
                   model_mask: Optional[np.ndarray] = None) -> torch.Tensor:
@@ -784,8 +808,7 @@ class FLJob:
             return totals
         plain = (self.cfg.server_optimizer == "avg" and
                  self.cfg.robust_noise <= 0)
-        if plain and not self.is_module_path and \
-                self.backend is not ops.mlp_torch:
+        if plain and self._hip_mlp:
             from ..ops import mlp_hip
             totals = mlp_hip.apply_aggregate(self.global_params, partial,
                                              mask_t, self._totals)
@@ -798,7 +821,7 @@ class FLJob:
         averaged = torch.where(upd.unsqueeze(1), newp, self.global_params)
         if self.cfg.robust_noise > 0:
             from ..comm.robust import add_noise
-            if getattr(self, "_noise_gen", None) is None:
+            if self._noise_gen is None:
                 # dedicated generator: every rank draws identical noise,
                 # keeping the lockstep-replicated control flow intact
                 self._noise_gen = torch.Generator(device=self.device)
@@ -807,7 +830,7 @@ class FLJob:
                               self._noise_gen)
             averaged = torch.where(upd.unsqueeze(1), noisy, averaged)
         if self.cfg.server_optimizer != "avg":
-            if getattr(self, "_server_opt", None) is None:
+            if self._server_opt is None:
                 from .server_opt import ServerOptimizer
                 kw = {"momentum": self.cfg.server_momentum} \
                     if self.cfg.server_momentum != 0 else {}
@@ -833,8 +856,7 @@ class FLJob:
         weights over all ranks."""
         from ..ops import krum_hip, orderstat_hip
         K, P = self.n_models, self.n_params
-        cfg = self.cfg
-        dev = self.device
+        cfg, dev = self.cfg, self.device
         krum = cfg.robust_agg == "multi_krum"
 
         def make(rows, models, w, ids):
@@ -845,23 +867,11 @@ class FLJob:
             return orderstat_hip.OrderStatPlan(
                 rows, models, w, K, cfg.robust_agg, cfg.robust_trim_frac)
 
-        tmpl = plan.template
-        slot = "_krum" if krum else "_orderstat"
-        hit = getattr(tmpl, slot, None) if tmpl is not None else None
-        if hit is not None and hit[0] is plan.sample_num:
-            op, sum_w = hit[1], hit[2]
-        else:
-            # per-template constants: uploaded once, reused every round
-            mo = plan.rows % K
-            sn = np.asarray(plan.sample_num)
-            w = sn[plan.rows // K, mo] if plan.rows.size else \
-                np.zeros(0, np.float32)
-            own = np.asarray(self.owned_workers, dtype=np.int64)
-            op = make(plan.rows, mo, w, own[plan.rows // K])
-            sum_w = torch.as_tensor(sn, dtype=torch.float32, device=dev) \
-                .reshape(-1, K).sum(dim=0)
-            if tmpl is not None:
-                setattr(tmpl, slot, (plan.sample_num, op, sum_w))
+        def build():
+            sn = torch.as_tensor(np.asarray(plan.sample_num),
+                                 dtype=torch.float32, device=dev)
+            return make(*self._pairs(plan)), sn.reshape(-1, K).sum(dim=0)
+        op, sum_w = self.cached(plan, "krum" if krum else "orderstat", build)
         bank = self.replicas
         if self.comm.distributed:
             sum_w = self.comm.all_reduce_(sum_w.clone())
@@ -884,10 +894,7 @@ class FLJob:
             self._krum_last = op
         else:
             orderstat_hip.aggregate(bank, op, partial[:, :P])
-        if getattr(op, "_has", None) is None:
-            op._has = torch.as_tensor((op.n > 0).astype(np.float32),
-                                      device=dev)
-        partial[:, P] = op._has
+        partial[:, P] = op.has(dev)
         self._partial_clean = False
         return sum_w
 
@@ -896,12 +903,23 @@ class FLJob:
         aggregation kept, in (score, id) order (on a GPU: one
         synchronisation and one copy, only here). Empty for every other
         robust_agg and before the first aggregation."""
-        op = getattr(self, "_krum_last", None)
-        if op is None:
-            return [np.zeros(0, dtype=np.int64)
-                    for _ in range(self.n_models)]
         from ..ops import krum_hip
-        return krum_hip.last_selection(op)
+        if self._krum_last is None:
+            return [np.zeros(0, np.int64) for _ in range(self.n_models)]
+        return krum_hip.last_selection(self._krum_last)
+
+    def _active_pairs(self, plan: TrainPlan):
+        """(act, sn, own): act [W, K] marks the uploads of positive weight
+        over ALL ranks (one small all_reduce when distributed); sn [nW, K]
+        and own [nW] are this rank's weights and global worker ids."""
+        own = np.asarray(self.owned_workers, dtype=np.int64)
+        sn = np.asarray(plan.sample_num).reshape(len(own), self.n_models)
+        act = np.zeros((self.n_workers, self.n_models), dtype=bool)
+        act[own] = sn > 0
+        if self.comm.distributed:
+            act = self.comm.all_reduce_(torch.as_tensor(
+                act.astype(np.float32), device=self.device)).cpu().numpy() > 0
+        return act, sn, own
 
     def _apply_secure_masks(self, plan: TrainPlan,
                             partial: torch.Tensor) -> None:
@@ -914,14 +932,7 @@ class FLJob:
         pair seeds advance per aggregation so masks never repeat."""
         from ..comm.secure_agg import mask_for
         K, P = self.n_models, self.n_params
-        W = self.n_workers
-        act = torch.zeros(W, K, device=self.device)
-        for wi, w in enumerate(self.owned_workers):
-            for m in range(K):
-                if plan.sample_num[wi, m] > 0:
-                    act[w, m] = 1.0
-        self.comm.all_reduce_(act)
-        act_np = act.cpu().numpy() > 0
+        act_np, _, _ = self._active_pairs(plan)
         self._secure_ctr += 1
         base = (self.cfg.dummy_arg * 1009 + self.curr_iter) * 65537 \
             + self._secure_ctr
@@ -943,35 +954,25 @@ class FLJob:
         the host work entirely."""
         from ..comm.secure_agg import build_mask_graph
         from ..ops.secagg_hip import SecaggPlan
-        K, W = self.n_models, self.n_workers
-        tmpl = plan.template
-        local = not self.comm.distributed
-        if local and tmpl is not None:
-            hit = getattr(tmpl, "_secagg", None)
-            if hit is not None and hit[0] is plan.sample_num:
-                return hit[1]
-        own = np.asarray(self.owned_workers, dtype=np.int64)
-        sn = np.asarray(plan.sample_num).reshape(len(own), K)
-        act = np.zeros((W, K), dtype=bool)
-        act[own] = sn > 0
-        if not local:
-            act_t = torch.as_tensor(act.astype(np.float32),
-                                    device=self.device)
-            self.comm.all_reduce_(act_t)
-            act = act_t.cpu().numpy() > 0
-        key = (act.tobytes(), sn.tobytes())
-        sp = self._secagg_plans.get(key)
-        if sp is None:
-            graph = build_mask_graph(act, self.cfg.secure_agg_degree,
-                                     self.cfg.dummy_arg, self.curr_iter)
-            wi, mo = np.nonzero(sn > 0)
-            sp = SecaggPlan(wi * K + mo, own[wi], mo, sn[wi, mo], K, graph)
-            if len(self._secagg_plans) >= 16:
-                self._secagg_plans.clear()
-            self._secagg_plans[key] = sp
-        if local and tmpl is not None:
-            tmpl._secagg = (plan.sample_num, sp)
-        return sp
+        K = self.n_models
+
+        def build():
+            act, sn, own = self._active_pairs(plan)
+            key = (act.tobytes(), sn.tobytes())
+            sp = self._secagg_plans.get(key)
+            if sp is None:
+                graph = build_mask_graph(act, self.cfg.secure_agg_degree,
+                                         self.cfg.dummy_arg, self.curr_iter)
+                wi, mo = np.nonzero(sn > 0)
+                sp = SecaggPlan(wi * K + mo, own[wi], mo, sn[wi, mo], K,
+                                graph)
+                if len(self._secagg_plans) >= 16:
+                    self._secagg_plans.clear()
+                self._secagg_plans[key] = sp
+            return sp
+        if self.comm.distributed:
+            return build()
+        return self.cached(plan, "secagg", build)
 
     def _secure_ring_partial(self, plan: TrainPlan,
                              partial: torch.Tensor) -> None:
@@ -1194,22 +1195,20 @@ class FLJob:
                             round_idx)
             self.logger.log({"Test/Acc": test_acc, "Test/Loss": test_loss},
                             round_idx)
+        # the stats run on all ranks: they all_reduce
         if self._robust_fused and self.cfg.robust_norm_bound > 0:
-            stats = self.clip_stats()          # all ranks: it all_reduces
-            if self.comm.is_root:
-                for m in range(self.n_models):
-                    if stats[m, 1] > 0:
-                        self.logger.log(
-                            {f"Robust/ClipFrac-m{m}":
-                             stats[m, 0] / stats[m, 1]}, round_idx)
+            self._log_fracs("Robust/ClipFrac", self.clip_stats(), round_idx)
         if self._compress:
-            stats = self.compress_stats()      # all ranks: it all_reduces
-            if self.comm.is_root:
-                for m in range(self.n_models):
-                    if stats[m, 1] > 0:
-                        self.logger.log(
-                            {f"Compress/SentFrac-m{m}":
-                             stats[m, 0] / stats[m, 1]}, round_idx)
+            self._log_fracs("Compress/SentFrac", self.compress_stats(),
+                            round_idx)
+
+    def _log_fracs(self, name: str, stats: np.ndarray, round_idx: int) -> None:
+        if self.comm.is_root:
+            for m in range(self.n_models):
+                if stats[m, 1] > 0:
+                    self.logger.log(
+                        {f"{name}-m{m}": stats[m, 0] / stats[m, 1]},
+                        round_idx)
 
     # ------------------------------------------------------------------
     # checkpointing (reference-compatible layout)

@@ -4,9 +4,10 @@ participants whose uploads lie closest to the others' are kept and averaged.
 HIP kernels (ops/hip/krum_kernels.hip) on a CUDA device, the specification
 (comm/robust.py, float32 mean) on CPU — so the option also runs under gloo.
 
-A KrumPlan is robust_hip.ClipPlan's pairs-by-model CSR restricted to the
-participants (aggregation weight > 0), plus every participant's tie-break id
-and the per-model counts n, f, q, s, computed on the host. On a GPU nothing
+A KrumPlan is robust_hip.ParticipantPlan (ClipPlan's pairs-by-model CSR
+restricted to the participants, aggregation weight > 0) plus every
+participant's tie-break id and the per-model counts f, q, s, computed on the
+host. On a GPU nothing
 is copied back in a steady-state aggregation: scores and the selection stay
 on the device until last_selection() asks for them.
 """
@@ -20,7 +21,7 @@ import torch
 
 from ..comm import robust as spec
 from . import hip_loader
-from .robust_hip import ClipPlan
+from .robust_hip import ParticipantPlan
 
 
 def tile() -> int:
@@ -76,7 +77,7 @@ def scratch_layout(n, n_split: int, rows_bound: int, budget: int):
     return slab, d_off, int(sizes.sum())
 
 
-class KrumPlan(ClipPlan):
+class KrumPlan(ParticipantPlan):
     def __init__(self, rows, models, weights, n_models: int, frac: float,
                  select: int = 0, ids=None):
         """Pair i = (bank row rows[i], model models[i], weight weights[i],
@@ -86,15 +87,9 @@ class KrumPlan(ClipPlan):
         ids = np.arange(len(rows), dtype=np.int64) if ids is None \
             else np.asarray(ids, dtype=np.int64)
         assert ids.shape == rows.shape
-        keep = np.asarray(weights, dtype=np.float32) > 0
-        models = np.asarray(models, dtype=np.int64)
-        super().__init__(rows[keep], models[keep],
-                         np.asarray(weights, dtype=np.float32)[keep],
-                         n_models)
-        # ClipPlan groups by model with a stable sort: ids follow it
-        self.ids = ids[keep][np.argsort(models[keep], kind="stable")]
+        super().__init__(rows, models, weights, n_models)
+        self.ids = ids[self.order]   # ids follow the grouping by model
         self.frac, self.select = float(frac), int(select)
-        self.n = np.diff(self.mod_off).astype(np.int64)
         cnt = [spec.krum_counts(n, frac, select) if n else (0, 0, 0)
                for n in self.n]
         self.f = np.array([c[0] for c in cnt], dtype=np.int32)

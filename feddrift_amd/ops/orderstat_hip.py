@@ -5,9 +5,9 @@ HIP kernel (ops/hip/orderstat_kernels.hip) on a CUDA device, the
 specification (comm/robust.py, float32) on CPU — so the option also runs
 under gloo.
 
-An OrderStatPlan is robust_hip.ClipPlan's pairs-by-model CSR restricted to
-the participants (aggregation weight > 0), plus the per-model trim count k,
-computed on the host.
+An OrderStatPlan is robust_hip.ParticipantPlan (ClipPlan's pairs-by-model
+CSR restricted to the participants, aggregation weight > 0) plus the
+per-model trim count k, computed on the host.
 """
 
 from __future__ import annotations
@@ -17,7 +17,7 @@ import torch
 
 from ..comm import robust as spec
 from . import hip_loader
-from .robust_hip import ClipPlan
+from .robust_hip import ParticipantPlan
 
 
 def tile() -> int:
@@ -37,20 +37,15 @@ def small_rows() -> int:
     return int(hip_loader.load().orderstat_small_rows())
 
 
-class OrderStatPlan(ClipPlan):
+class OrderStatPlan(ParticipantPlan):
     def __init__(self, rows, models, weights, n_models: int, kind: str,
                  frac: float = 0.0):
         """Pair i = (bank row rows[i], model models[i], weight weights[i]);
         any order. Pairs with weight <= 0 do not participate."""
         if kind not in spec.ORDER_KINDS[1:]:
             raise ValueError(f"'{kind}' is not an order statistic")
-        keep = np.asarray(weights, dtype=np.float32) > 0
-        super().__init__(np.asarray(rows, dtype=np.int64)[keep],
-                         np.asarray(models, dtype=np.int64)[keep],
-                         np.asarray(weights, dtype=np.float32)[keep],
-                         n_models)
+        super().__init__(rows, models, weights, n_models)
         self.kind, self.frac = kind, float(frac)
-        self.n = np.diff(self.mod_off).astype(np.int64)
         self.k = np.array([spec.trim_count(kind, frac, n) for n in self.n],
                           dtype=np.int32)
         self._k_dev = None

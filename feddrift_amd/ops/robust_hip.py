@@ -47,6 +47,7 @@ class ClipPlan:
         models = np.asarray(models, dtype=np.int64)
         weights = np.asarray(weights, dtype=np.float32)
         order = np.argsort(models, kind="stable")
+        self.order = order           # plan position -> position as given
         self.n_models = int(n_models)
         self.rows = rows[order]
         self.models = models[order]
@@ -82,6 +83,29 @@ class ClipPlan:
             self._dev = (t(self.mod_off), t(self.rows),
                          t(self.models.astype(np.int32)), t(self.weights))
         return self._dev
+
+
+class ParticipantPlan(ClipPlan):
+    """ClipPlan restricted to the participants (aggregation weight > 0):
+    what the row-reading aggregations (order statistics, Multi-Krum) share.
+    `order` indexes the pairs as given; n[m] counts model m's participants."""
+
+    def __init__(self, rows, models, weights, n_models: int):
+        weights = np.asarray(weights, dtype=np.float32)
+        keep = np.nonzero(weights > 0)[0]
+        super().__init__(np.asarray(rows, dtype=np.int64)[keep],
+                         np.asarray(models, dtype=np.int64)[keep],
+                         weights[keep], n_models)
+        self.order = keep[self.order]
+        self.n = np.diff(self.mod_off).astype(np.int64)
+        self._has = None
+
+    def has(self, device) -> torch.Tensor:
+        """[K] float: 1 for a model with a participant (uploaded once)."""
+        if self._has is None:
+            self._has = torch.as_tensor((self.n > 0).astype(np.float32),
+                                        device=device)
+        return self._has
 
 
 def new_counts(n_models: int, device) -> torch.Tensor:

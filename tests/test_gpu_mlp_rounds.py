@@ -59,5 +59,7 @@ def test_fljob_rounds_default_path(tmp_path):
     assert figs["mean/bound"] <= 1.0
     # the rounds went through the per-template staging and constant cache
     tmpl = job.algo._tmpl
-    assert tmpl._stage["buf"].shape[1] == len(tmpl.rows)
-    assert tmpl._dev[0].numel() == len(tmpl.rows)
+    stage = tmpl.cache["stage", job.cfg.epochs][1]
+    train = tmpl.cache["train"][1]
+    assert stage["buf"].shape[1] == len(tmpl.rows)
+    assert train[0].numel() == len(tmpl.rows)
