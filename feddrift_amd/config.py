@@ -96,24 +96,34 @@ class Config:
     # mu * (w - w0) to the gradient, w0 = the global model the client got
     # this round (0 = plain local training, bit for bit)
     fedprox_mu: float = 0.0
-    # upload compression: none|topk. topk sends the compress_ratio share of
-    # largest-magnitude coordinates of every trained row's update and, with
-    # compress_error_feedback=1, adds what was held back to the next update
+    # upload compression: none|topk|quant|topk_quant. topk sends the
+    # compress_ratio share of largest-magnitude coordinates of every trained
+    # row's update; quant sends every coordinate stochastically rounded to
+    # compress_bits bits against the row's largest magnitude; topk_quant
+    # quantises what topk sends. With compress_error_feedback=1 what was
+    # held back (the quantisation error included) joins the next update
     upload_compress: str = "none"
     compress_ratio: float = 0.01         # share of a row sent, in (0, 1]
     compress_error_feedback: int = 1
+    compress_bits: int = 8               # per coordinate, sign included
 
     def __post_init__(self):
         self.dataset_norm = "MNIST" if self.dataset.lower() == "mnist" else self.dataset
-        if self.upload_compress not in ("none", "topk"):
-            raise ValueError("upload_compress must be one of none, topk, got "
-                             f"'{self.upload_compress}'")
+        if self.upload_compress not in ("none", "topk", "quant",
+                                        "topk_quant"):
+            raise ValueError("upload_compress must be one of none, topk, "
+                             f"quant, topk_quant, got '{self.upload_compress}'")
         if not 0.0 < self.compress_ratio <= 1.0:
             raise ValueError("compress_ratio must lie in (0, 1], got "
                              f"{self.compress_ratio}")
         if self.compress_error_feedback not in (0, 1):
             raise ValueError("compress_error_feedback must be 0 or 1, got "
                              f"{self.compress_error_feedback}")
+        if isinstance(self.compress_bits, bool) or \
+                not isinstance(self.compress_bits, int) or \
+                not 2 <= self.compress_bits <= 16:
+            raise ValueError("compress_bits must be an integer in [2, 16], "
+                             f"got {self.compress_bits!r}")
         if not (self.fedprox_mu >= 0.0 and self.fedprox_mu != float("inf")):
             raise ValueError("fedprox_mu must be finite and >= 0, got "
                              f"{self.fedprox_mu}")

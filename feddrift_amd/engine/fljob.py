@@ -351,16 +351,22 @@ class FLJob:
             # a norm bound) counts here, so clip_stats() stays as it is
             self._clip_unbounded = robust_hip.new_counts(self.n_models,
                                                          self.device)
-        # upload_compress=topk: a pass over the trained rows between train
-        # and clip (ops/compress_hip.py); the residual bank is the pairs'
-        # error-feedback memory, owned by the replica row like the
-        # optimizer state
+        # upload_compress=topk|quant|topk_quant: a pass over the trained
+        # rows between train and clip (ops/compress_hip.py); the residual
+        # bank is the pairs' error-feedback memory, owned by the replica row
+        # like the optimizer state
         self._compress = cfg.upload_compress != "none"
         self._residual: Optional[torch.Tensor] = None
         if self._compress:
-            from ..comm.compress import keep_count
+            from ..comm.compress import keep_count, quant_key
             from ..ops import compress_hip
-            self._compress_k = keep_count(cfg.compress_ratio, P)
+            # quant reads no ratio: every non-zero coordinate travels (k = 0)
+            self._compress_k = 0 if cfg.upload_compress == "quant" else \
+                keep_count(cfg.compress_ratio, P)
+            # the quantiser's Philox key and the compress-pass counter, which
+            # every rank advances once per train() call
+            self._quant_key = quant_key(cfg.dummy_arg, self.curr_iter)
+            self._compress_ctr = 0
             self._compress_counts = compress_hip.new_counts(self.n_models,
                                                             self.device)
             if cfg.compress_error_feedback == 1:
@@ -609,6 +615,8 @@ class FLJob:
         if route.launch == "synced":
             self.sync_replicas()
         if empty:
+            # no pass runs, but the ranks' pass counters stay in step
+            self._compress_pass(plan)
             return
         if route.launch == "module":
             self.mod_engine.train(self.global_params, self.replicas, plan,
@@ -700,16 +708,32 @@ class FLJob:
             self._clip_counts if bounded else self._clip_unbounded)
 
     def _compress_pass(self, plan: TrainPlan) -> None:
-        """upload_compress=topk: one pass over the trained rows, whatever
-        their aggregation weight (ops/compress_hip.py)."""
-        if not self._compress or plan.rows.size == 0:
+        """upload_compress: one pass over the trained rows, whatever their
+        aggregation weight (ops/compress_hip.py). Every call takes the next
+        value of the pass counter, which the quantiser's draws read: also a
+        call on an empty plan, so that ranks with and without trained rows
+        draw from the same pass."""
+        if not self._compress:
+            return
+        ctr = self._compress_ctr
+        self._compress_ctr = (ctr + 1) & 0xFFFFFFFF
+        if plan.rows.size == 0:
             return
         from ..ops import compress_hip
-        cp = self.cached(plan, "compress", lambda: compress_hip.CompressPlan(
-            *self._pairs(plan)[:2], self.n_models))
-        compress_hip.topk(self.replicas, cp, self.global_params,
-                          self._residual, self._compress_k,
-                          self._compress_counts)
+
+        def build():
+            rows, mo, _, workers = self._pairs(plan)
+            return compress_hip.CompressPlan(rows, mo, self.n_models, workers)
+        cp = self.cached(plan, "compress", build)
+        if self.cfg.upload_compress == "topk":
+            compress_hip.topk(self.replicas, cp, self.global_params,
+                              self._residual, self._compress_k,
+                              self._compress_counts)
+        else:
+            compress_hip.quant(self.replicas, cp, self.global_params,
+                               self._residual, self._compress_k,
+                               self.cfg.compress_bits, self._quant_key, ctr,
+                               self._compress_counts)
 
     def _drain_counts(self, counts: Optional[torch.Tensor]) -> np.ndarray:
         """[K, 2] int64: a per-model device counter summed across ranks
@@ -1199,8 +1223,23 @@ class FLJob:
         if self._robust_fused and self.cfg.robust_norm_bound > 0:
             self._log_fracs("Robust/ClipFrac", self.clip_stats(), round_idx)
         if self._compress:
-            self._log_fracs("Compress/SentFrac", self.compress_stats(),
+            stats = self.compress_stats()
+            self._log_fracs("Compress/SentFrac", stats, round_idx)
+            self._log_fracs("Compress/WireFrac", self._wire_stats(stats),
                             round_idx)
+
+    def _wire_stats(self, stats: np.ndarray) -> np.ndarray:
+        """[K, 2] (bits on the wire, bits of the dense float32 rows) from
+        drained compress_stats() counters (comm/compress.py:wire_bits)."""
+        from ..comm.compress import wire_bits
+        P = self.n_params
+        out = np.zeros((self.n_models, 2), dtype=np.int64)
+        for m in range(self.n_models):
+            out[m, 0] = wire_bits(self.cfg.upload_compress, stats[m, 0],
+                                  stats[m, 1] // P, P,
+                                  self.cfg.compress_bits)
+            out[m, 1] = 32 * stats[m, 1]
+        return out
 
     def _log_fracs(self, name: str, stats: np.ndarray, round_idx: int) -> None:
         if self.comm.is_root:
