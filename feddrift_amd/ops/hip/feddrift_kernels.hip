@@ -15,6 +15,13 @@
 //    per-thread ownership partition (no atomics: shared entries add
 //    their partial sums in a fixed order), and applies the
 //    SGD/Adam(amsgrad, wd) update in-place. Adam state stays in HBM.
+//  * mlp_train_small_kernel: the same launch for the five compile-time
+//    shapes of the drift path (the flagship). Samples, activations and the
+//    gradient accumulators live in registers; a wave reduce-scatter leaves
+//    each parameter entry's gradient total in one owner lane, which keeps
+//    the entry's weight and Adam state in registers for the whole E-step
+//    loop and steps it there. LDS holds only the weights the sample
+//    pipeline reads; nothing is accumulated through LDS atomics.
 //  * mlp_eval_kernel: ONE launch per accuracy/loss sweep (the K-models x
 //    C-clients matrices, prequential testing). One workgroup per data
 //    window; per-thread sample loop + LDS tree reduction; one global
@@ -364,11 +371,188 @@ void mlp_train_kernel(TrainArgs a) {
 // ---------------------------------------------------------------------------
 // specialized small-MLP training kernel: the whole per-sample pipeline and
 // the per-thread gradient accumulators live in REGISTERS (compile-time
-// D/H/O, fully unrolled); gradients reduce by wave shuffles, then one LDS
-// add per entry (single-wave blocks) or the waves' sums added in wave
-// order (256-thread blocks). This is the SEA/SINE/CIRCLE flagship path — the generic
-// kernel above stays latency-bound on LDS round trips for these shapes.
+// D/H/O, fully unrolled). The gradients meet in a wave reduce-SCATTER:
+// entry p's total ends in lane bitrev6(p) and nowhere else, and that owner
+// lane keeps w[p] and the entry's Adam state in registers from the first
+// load to the last store and steps the entry itself. LDS holds only the
+// weights the sample pipeline reads (and, for 256-thread blocks, the
+// waves' sums, which wave 0's owner lanes add in wave order). This is the
+// SEA/SINE/CIRCLE flagship path: about ten one-wave blocks per launch, so
+// the length of one wave's dependent chain per step is all that counts.
 // ---------------------------------------------------------------------------
+
+// one sample's forward + backward, added into this lane's accumulators.
+// Which products fuse into an FMA is written out here, not left to the
+// compiler's contraction (it moves with the surrounding code, and the
+// round's results with it): the roundings are the ones this pipeline has
+// always had. Hidden layer, dz1 and the weight gradients are FMA chains;
+// the output dot products add rounded products (after a fused first term
+// where the input width is odd); the output-bias gradient fuses the last
+// product of dz with its own sum.
+template <int TD, int TH, int TO, int KIND, int TP>
+__device__ __forceinline__ void small_sample_grad(const float (&x)[TD],
+                                                  const int yi,
+                                                  const float* w,
+                                                  const float inv_n,
+                                                  float (&gacc)[TP]) {
+#pragma clang fp contract(off)
+  constexpr int HD = TH * TD;
+  constexpr int OH = TO * TH;
+  if constexpr (KIND == KIND_FNN) {
+    float act[TH], dzo[TO];
+#pragma unroll
+    for (int h = 0; h < TH; ++h) {
+      float z = w[HD + h];
+#pragma unroll
+      for (int d = 0; d < TD; ++d) z = __builtin_fmaf(w[h * TD + d], x[d], z);
+      act[h] = z > 0.f ? z : 0.f;
+    }
+    float zmax = -1e30f;
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+      float z = w[HD + TH + OH + o];
+#pragma unroll
+      for (int h = 0; h < TH; ++h) z += w[HD + TH + o * TH + h] * act[h];
+      dzo[o] = z;
+      zmax = fmaxf(zmax, z);
+    }
+    float zsum = 0.f;
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+      dzo[o] = __expf(dzo[o] - zmax);
+      zsum += dzo[o];
+    }
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+      float sm = dzo[o] / zsum;
+      if (o == yi) sm -= 1.f;
+      dzo[o] = sm * inv_n;
+      gacc[HD + TH + OH + o] =
+          __builtin_fmaf(sm, inv_n, gacc[HD + TH + OH + o]);
+    }
+    float dza[TH];
+#pragma unroll
+    for (int h = 0; h < TH; ++h) {
+      float s = 0.f;
+#pragma unroll
+      for (int o = 0; o < TO; ++o)
+        s = __builtin_fmaf(dzo[o], w[HD + TH + o * TH + h], s);
+      dza[h] = act[h] > 0.f ? s : 0.f;
+    }
+#pragma unroll
+    for (int h = 0; h < TH; ++h) {
+#pragma unroll
+      for (int d = 0; d < TD; ++d)
+        gacc[h * TD + d] = __builtin_fmaf(dza[h], x[d], gacc[h * TD + d]);
+      gacc[HD + h] += dza[h];
+    }
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+#pragma unroll
+      for (int h = 0; h < TH; ++h)
+        gacc[HD + TH + o * TH + h] =
+            __builtin_fmaf(dzo[o], act[h], gacc[HD + TH + o * TH + h]);
+    }
+  } else {  // LR
+    float p_[TO], dzo[TO];
+    float pmax = -1e30f;
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+      float z = w[TO * TD + o];
+#pragma unroll
+      for (int d = 0; d < TD; ++d) {
+        if (d < (TD & 1)) z = __builtin_fmaf(w[o * TD + d], x[d], z);
+        else z += w[o * TD + d] * x[d];
+      }
+      p_[o] = 1.f / (1.f + __expf(-z));
+      pmax = fmaxf(pmax, p_[o]);
+    }
+    float psum = 0.f;
+#pragma unroll
+    for (int o = 0; o < TO; ++o) psum += __expf(p_[o] - pmax);
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+      float sm = __expf(p_[o] - pmax) / psum;
+      if (o == yi) sm -= 1.f;
+      // dz = dp * sigmoid' = dp * p (1-p)
+      const float dp = sm * inv_n * p_[o];
+      dzo[o] = dp * (1.f - p_[o]);
+      gacc[TO * TD + o] =
+          __builtin_fmaf(dp, 1.f - p_[o], gacc[TO * TD + o]);
+    }
+#pragma unroll
+    for (int o = 0; o < TO; ++o) {
+#pragma unroll
+      for (int d = 0; d < TD; ++d)
+        gacc[o * TD + d] = __builtin_fmaf(dzo[o], x[d], gacc[o * TD + d]);
+    }
+  }
+}
+
+// Lane that ends up holding entry p of the wave reduce-scatter below.
+__device__ __forceinline__ int bitrev6(int p) {
+  return (int)(__brev((unsigned)p) >> 26);
+}
+
+// One exchange of the reduce-scatter at lane distance S. Lanes with bit S
+// clear keep entry `a`, lanes with bit S set keep entry `b`; each lane adds
+// its partner's (lane ^ S) partial of the entry it keeps to its own.
+template <int S>
+__device__ __forceinline__ float scatter_exchange_add(const float a,
+                                                      const float b,
+                                                      const int lane) {
+  if constexpr (S == 32) {
+    // half-wave swap: lanes 32..63 of the first operand trade places with
+    // lanes 0..31 of the second, so both operands then hold (own partial,
+    // partner's partial) of the kept entry: one swap, one add, no select,
+    // nothing on the LDS pipe
+    const auto r = __builtin_amdgcn_permlane32_swap(
+        __float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  } else if constexpr (S == 16) {
+    // the same between the odd 16-lane rows of the first operand and the
+    // even rows of the second
+    const auto r = __builtin_amdgcn_permlane16_swap(
+        __float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  } else {
+    const bool hi = (lane & S) != 0;
+    const float keep = hi ? b : a;
+    const float send = hi ? a : b;
+    return keep + __shfl_xor(send, S, 64);
+  }
+}
+
+// Wave reduce-scatter of N per-lane partials, levels S = 32, 16, ..., 1.
+// Level S pairs the entries still held two by two (split on the lowest
+// entry bit not yet used) and halves their number; an odd one out pairs
+// with a zero nobody reads. Entry p's total ends in lane bitrev6(p): that
+// lane's return value. For TP = 38 the levels move 19+10+5+3+2+1 = 40
+// registers, where an all-reduce tree moves 6 x 38.
+//
+// The sum of an entry has the order of the shuffle-down tree
+// (v[i] + v[i + S] for i < S at level S) bit for bit: every lane that
+// keeps the entry adds the same two values, commuted in half of them.
+// All register indices are compile-time, so nothing spills.
+template <int N, int S>
+struct ScatterReduce {
+  static __device__ __forceinline__ float run(const float (&r)[N],
+                                              const int lane) {
+    constexpr int M = (N + 1) / 2;
+    float o[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k)
+      o[k] = scatter_exchange_add<S>(r[2 * k],
+                                     2 * k + 1 < N ? r[2 * k + 1] : 0.f,
+                                     lane);
+    if constexpr (S == 1) {
+      static_assert(M == 1, "reduce-scatter holds at most 64 entries");
+      return o[0];
+    } else {
+      return ScatterReduce<M, S / 2>::run(o, lane);
+    }
+  }
+};
 
 template <int TD, int TH, int TO, int KIND, int BS>
 __global__ __launch_bounds__(BS)
@@ -376,222 +560,199 @@ void mlp_train_small_kernel(TrainArgs a) {
   constexpr int TP = (KIND == KIND_FNN)
                          ? (TH * TD + TH + TO * TH + TO)
                          : (TO * TD + TO);
-  constexpr int HD = TH * TD;
-  constexpr int OH = TO * TH;
+  static_assert(TP <= 64, "one owner lane per parameter entry");
+  constexpr int NW = BS / 64;
+  // a step of up to PF trips of the sample loop loads all its samples up
+  // front (one wave per SIMD may hold 512 VGPRs; see ops/hip/README.md)
+  constexpr int PF = 8;
   const int g = blockIdx.x;
-  const int64_t row = a.rows[g];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
+  const int p_own = bitrev6(lane);
+  // the lane that holds entry p_own's total after the reduce and steps it
+  const bool owner = tid < 64 && p_own < TP;
+  const bool adam = (a.opt == OPT_ADAM);
 
   __shared__ __attribute__((aligned(16))) float w[TP];
-  __shared__ __attribute__((aligned(16))) float grad[TP];
-  // Adam state LDS-resident for the whole E-step loop (HBM round trips
-  // per optimizer step removed; staged back at the end)
-  __shared__ __attribute__((aligned(16))) float sm_[TP], sv_[TP], svm_[TP];
-  __shared__ float msk[TD > 0 ? TD : 1];
-  __shared__ int tstep;
-  __shared__ float b1pow, b2pow;   // beta^t maintained incrementally
+  __shared__ float wsum[NW > 1 ? NW : 1][NW > 1 ? TP : 1];
 
-  stage_weights(a, g, row, w);
-  if (a.x_mask && tid < TD) msk[tid] = a.x_mask[(int64_t)g * TD + tid];
-  const bool adam = (a.opt == OPT_ADAM);
-  if (adam) {
-    for (int p = tid; p < TP; p += BS) {
-      sm_[p] = a.m[row * TP + p];
-      sv_[p] = a.v[row * TP + p];
-      svm_[p] = a.vmax[row * TP + p];
-    }
-    if (tid == 0) {
-      tstep = a.t[row];
-      b1pow = powf(0.9f, (float)tstep);
-      b2pow = powf(0.999f, (float)tstep);
+  // every load that depends on nothing, or only on rows[g], issues here
+  const int64_t row = a.rows[g];
+  const int64_t e0 = (int64_t)g * a.E;
+  int64_t off_nx = 0;
+  int n_nx = 0;
+  if (a.E > 0) {
+    off_nx = a.step_off[e0];
+    n_nx = (int)a.step_len[e0];
+  }
+  float mk[TD];
+#pragma unroll
+  for (int d = 0; d < TD; ++d)
+    mk[d] = a.x_mask ? a.x_mask[(int64_t)g * TD + d] : 1.f;
+  const bool fuse_partial = a.partial && a.sample_w;
+  const float sw = fuse_partial ? a.sample_w[g] : 0.f;
+  const int64_t pbase =
+      fuse_partial ? (int64_t)a.model_of[g] * (TP + 1) : 0;
+  const float lr_ = a.lr[row];
+  float wreg = 0.f, mreg = 0.f, vreg = 0.f, vmreg = 0.f;
+  if (owner) {
+    // straight from the GLOBAL model row when the broadcast is fused
+    wreg = a.in_params
+               ? a.in_params[(int64_t)a.model_of[g] * TP + p_own]
+               : a.params[row * TP + p_own];
+    if (adam) {
+      mreg = a.m[row * TP + p_own];
+      vreg = a.v[row * TP + p_own];
+      vmreg = a.vmax[row * TP + p_own];
     }
   }
+  // every lane keeps its own step count and beta^t (incrementally)
+  int tstep = adam ? a.t[row] : 0;
+  float b1pow = 1.f, b2pow = 1.f;
+  if (adam) {
+    b1pow = powf(0.9f, (float)tstep);
+    b2pow = powf(0.999f, (float)tstep);
+  }
+  // FedProx anchor: the value the entry was staged with
+  const float w0 = wreg;
+  if (owner) w[p_own] = wreg;
   __syncthreads();
 
   for (int e = 0; e < a.E; ++e) {
-    const int64_t off = a.step_off[(int64_t)g * a.E + e];
-    const int n = (int)a.step_len[(int64_t)g * a.E + e];
+    const int64_t off = off_nx;
+    const int n = n_nx;
+    if (e + 1 < a.E) {  // next step's window, ahead of this step's work
+      off_nx = a.step_off[e0 + e + 1];
+      n_nx = (int)a.step_len[e0 + e + 1];
+    }
     if (n == 0) continue;
     const float inv_n = 1.0f / (float)n;
-
-    for (int p = tid; p < TP; p += BS) grad[p] = 0.f;
-    __syncthreads();
 
     float gacc[TP];
 #pragma unroll
     for (int p = 0; p < TP; ++p) gacc[p] = 0.f;
 
-    for (int i = tid; i < n; i += BS) {
-      float x[TD];
+    if (n <= PF * BS) {
+      // all of the step's samples in flight at once, then the same
+      // per-lane order of accumulation (i = tid, tid + BS, ...)
+      float xr[PF][TD];
+      int yr[PF];
 #pragma unroll
-      for (int d = 0; d < TD; ++d) {
-        x[d] = a.x[(off + i) * TD + d];
-        if (a.x_mask) x[d] *= msk[d];
+      for (int k = 0; k < PF; ++k) {
+        const int i = tid + k * BS;
+        const bool on = i < n;
+#pragma unroll
+        for (int d = 0; d < TD; ++d)
+          xr[k][d] = on ? a.x[(off + i) * TD + d] : 0.f;
+        yr[k] = on ? (int)a.y[off + i] : 0;
       }
-      const int yi = (int)a.y[off + i];
-      if constexpr (KIND == KIND_FNN) {
-        float act[TH], dzo[TO];
 #pragma unroll
-        for (int h = 0; h < TH; ++h) {
-          float z = w[HD + h];
+      for (int k = 0; k < PF; ++k) {
+        if (tid + k * BS < n) {
+          if (a.x_mask) {
 #pragma unroll
-          for (int d = 0; d < TD; ++d) z += w[h * TD + d] * x[d];
-          act[h] = z > 0.f ? z : 0.f;
+            for (int d = 0; d < TD; ++d) xr[k][d] *= mk[d];
+          }
+          small_sample_grad<TD, TH, TO, KIND, TP>(xr[k], yr[k], w, inv_n,
+                                                  gacc);
         }
-        float zmax = -1e30f;
+      }
+    } else {
+      for (int i = tid; i < n; i += BS) {
+        float x[TD];
 #pragma unroll
-        for (int o = 0; o < TO; ++o) {
-          float z = w[HD + TH + OH + o];
-#pragma unroll
-          for (int h = 0; h < TH; ++h) z += w[HD + TH + o * TH + h] * act[h];
-          dzo[o] = z;
-          zmax = fmaxf(zmax, z);
+        for (int d = 0; d < TD; ++d) {
+          x[d] = a.x[(off + i) * TD + d];
+          if (a.x_mask) x[d] *= mk[d];
         }
-        float zsum = 0.f;
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-          dzo[o] = __expf(dzo[o] - zmax);
-          zsum += dzo[o];
-        }
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-          float sm = dzo[o] / zsum;
-          if (o == yi) sm -= 1.f;
-          dzo[o] = sm * inv_n;
-        }
-        float dza[TH];
-#pragma unroll
-        for (int h = 0; h < TH; ++h) {
-          float s = 0.f;
-#pragma unroll
-          for (int o = 0; o < TO; ++o) s += dzo[o] * w[HD + TH + o * TH + h];
-          dza[h] = act[h] > 0.f ? s : 0.f;
-        }
-#pragma unroll
-        for (int h = 0; h < TH; ++h) {
-#pragma unroll
-          for (int d = 0; d < TD; ++d) gacc[h * TD + d] += dza[h] * x[d];
-          gacc[HD + h] += dza[h];
-        }
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-#pragma unroll
-          for (int h = 0; h < TH; ++h)
-            gacc[HD + TH + o * TH + h] += dzo[o] * act[h];
-          gacc[HD + TH + OH + o] += dzo[o];
-        }
-      } else {  // LR
-        float p_[TO], dzo[TO];
-        float pmax = -1e30f;
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-          float z = w[TO * TD + o];
-#pragma unroll
-          for (int d = 0; d < TD; ++d) z += w[o * TD + d] * x[d];
-          p_[o] = 1.f / (1.f + __expf(-z));
-          pmax = fmaxf(pmax, p_[o]);
-        }
-        float psum = 0.f;
-#pragma unroll
-        for (int o = 0; o < TO; ++o) psum += __expf(p_[o] - pmax);
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-          float sm = __expf(p_[o] - pmax) / psum;
-          if (o == yi) sm -= 1.f;
-          dzo[o] = sm * inv_n * p_[o] * (1.f - p_[o]);
-        }
-#pragma unroll
-        for (int o = 0; o < TO; ++o) {
-#pragma unroll
-          for (int d = 0; d < TD; ++d) gacc[o * TD + d] += dzo[o] * x[d];
-          gacc[TO * TD + o] += dzo[o];
-        }
+        const int yi = (int)a.y[off + i];
+        small_sample_grad<TD, TH, TO, KIND, TP>(x, yi, w, inv_n, gacc);
       }
     }
 
-    // reduce: wave shuffles LEVEL-major — all TP entries' bpermutes issue
-    // back-to-back per level, so the LDS-pipe latency is paid ~once per
-    // level instead of once per (entry, level) chain (entry-major measured
-    // ~24 us of pure ds_bpermute wait per launch on SEA shapes)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-      float sh[TP];
-#pragma unroll
-      for (int p = 0; p < TP; ++p) sh[p] = __shfl_down(gacc[p], s, 64);
-#pragma unroll
-      for (int p = 0; p < TP; ++p) gacc[p] += sh[p];
-    }
-    if constexpr (BS == 64) {
-      if (lane == 0) {
-#pragma unroll
-        for (int p = 0; p < TP; ++p) atomicAdd(&grad[p], gacc[p]);
-      }
+    float tot = ScatterReduce<TP, 32>::run(gacc, lane);
+    if constexpr (NW == 1) {
+      // the total used to land in a zeroed LDS slot by an atomic add;
+      // 0 + total keeps that result where the total is -0
+      tot = 0.f + tot;
     } else {
-      // several waves: their sums meet in wave order, not in the order the
-      // LDS atomics happen to land, so a launch repeats bit for bit
-      __shared__ float wsum[BS / 64][TP];
-      if (lane == 0) {
-#pragma unroll
-        for (int p = 0; p < TP; ++p) wsum[tid >> 6][p] = gacc[p];
-      }
+      // several waves: their sums meet in wave order, so a launch repeats
+      // bit for bit
+      if (p_own < TP) wsum[tid >> 6][p_own] = tot;
       __syncthreads();
-      for (int p = tid; p < TP; p += BS) {
-        float s = wsum[0][p];
+      if (owner) {
+        tot = wsum[0][p_own];
 #pragma unroll
-        for (int wv = 1; wv < BS / 64; ++wv) s += wsum[wv][p];
-        grad[p] = s;
+        for (int wv = 1; wv < NW; ++wv) tot += wsum[wv][p_own];
       }
     }
-    __syncthreads();
 
-    // optimizer step, all state in LDS (numerics match ops/mlp_torch.py)
-    if (a.mu != 0.f) {
-      // FedProx pull (wave-uniform branch); entry p is folded in by the
-      // thread that steps it below. The anchor row is a few dozen
-      // L2-resident floats.
-      const float* w0 = prox_anchor(a, g, row);
-      for (int p = tid; p < TP; p += BS)
-        grad[p] += a.mu * (w[p] - w0[p]);
+    // optimizer step in the owner lane's registers (numerics match
+    // ops/mlp_torch.py)
+    if (adam) {
+      tstep += 1;
+      b1pow *= 0.9f;
+      b2pow *= 0.999f;
     }
-    if (!adam) {
-      const float lr_ = a.lr[row];
-      for (int p = tid; p < TP; p += BS) w[p] -= lr_ * grad[p];
-    } else {
-      if (tid == 0) {
-        tstep += 1;
-        b1pow *= 0.9f;
-        b2pow *= 0.999f;
-      }
-      __syncthreads();
-      const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-      const float bc1 = 1.f - b1pow;
-      const float bc2 = 1.f - b2pow;
-      const float lr_ = a.lr[row];
-      for (int p = tid; p < TP; p += BS) {
-        const float gr = grad[p] + a.wd * w[p];
-        const float mn = b1 * sm_[p] + (1.f - b1) * gr;
-        const float vn = b2 * sv_[p] + (1.f - b2) * gr * gr;
-        sm_[p] = mn;
-        sv_[p] = vn;
-        const float vm = fmaxf(svm_[p], vn);
-        svm_[p] = vm;
+    if (owner) {
+      // Which products fuse into an FMA is written out, not left to the
+      // compiler's contraction: the roundings below are the ones this
+      // step has always had (m adds two rounded products), so results do
+      // not move when the code around them does.
+#pragma clang fp contract(off)
+      float gr = tot;
+      if (a.mu != 0.f) gr = __builtin_fmaf(a.mu, wreg - w0, gr);  // FedProx
+      if (!adam) {
+        wreg = __builtin_fmaf(-lr_, gr, wreg);
+      } else {
+        const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+        const float bc1 = 1.f - b1pow;
+        const float bc2 = 1.f - b2pow;
+        gr = __builtin_fmaf(a.wd, wreg, gr);
+        const float mn = b1 * mreg + (1.f - b1) * gr;
+        const float vn = __builtin_fmaf((1.f - b2) * gr, gr, b2 * vreg);
+        mreg = mn;
+        vreg = vn;
+        const float vm = fmaxf(vmreg, vn);
+        vmreg = vm;
         const float denom = sqrtf(vm / bc2) + eps;
-        w[p] -= lr_ * (mn / bc1) / denom;
+        wreg -= lr_ * (mn / bc1) / denom;
       }
+      w[p_own] = wreg;
     }
+    // the next step's samples read the new weights (and, with several
+    // waves, wsum is free again)
     __syncthreads();
   }
 
-  if (adam) {
-    for (int p = tid; p < TP; p += BS) {
-      a.m[row * TP + p] = sm_[p];
-      a.v[row * TP + p] = sv_[p];
-      a.vmax[row * TP + p] = svm_[p];
+  if (owner) {
+    if (adam) {
+      a.m[row * TP + p_own] = mreg;
+      a.v[row * TP + p_own] = vreg;
+      a.vmax[row * TP + p_own] = vmreg;
+      if (tid == 0) a.t[row] = tstep;
     }
-    if (tid == 0) a.t[row] = tstep;
+    a.params[row * TP + p_own] = wreg;
+    if (fuse_partial && sw > 0.f) {
+      atomicAdd(&a.partial[pbase + p_own], sw * wreg);
+      if (tid == 0) atomicAdd(&a.partial[pbase + TP], sw);
+    }
   }
-  write_back(a, g, row, w);
+}
+
+// test-only: the train kernel's reduce-scatter on one wave. vals is
+// [64, TP] (lane-major); out[p] is entry p's total as its owner lane holds it
+template <int TP>
+__global__ __launch_bounds__(64)
+void train_reduce_probe_kernel(const float* __restrict__ vals,
+                               float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  float r[TP];
+#pragma unroll
+  for (int p = 0; p < TP; ++p) r[p] = vals[lane * TP + p];
+  const float tot = ScatterReduce<TP, 32>::run(r, lane);
+  const int p_own = bitrev6(lane);
+  if (p_own < TP) out[p_own] = tot;
 }
 
 #define SMALL_SHAPE_LIST(X)      \
@@ -1098,6 +1259,32 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
   TORCH_CHECK(hipGetLastError() == hipSuccess, "mlp_train_kernel launch");
 }
 
+// test-only: the small train kernel's wave reduce-scatter on vals [64, TP]
+torch::Tensor train_reduce_probe_hip(torch::Tensor vals) {
+  check_f32_2d(vals, "vals");
+  TORCH_CHECK(vals.dim() == 2 && vals.size(0) == 64,
+              "train_reduce_probe: vals must be [64, TP]");
+  const int TP = vals.size(1);
+  auto out = torch::zeros({TP}, vals.options());
+  auto stream = c10::hip::getCurrentHIPStream();
+  bool found = false;
+#define TRY_PROBE(SD, SH, SO, SK)                                          \
+  if (!found && TP == (SK == KIND_FNN ? SH * SD + SH + SO * SH + SO        \
+                                      : SO * SD + SO)) {                   \
+    hipLaunchKernelGGL((train_reduce_probe_kernel<(                        \
+                           SK == KIND_FNN ? SH * SD + SH + SO * SH + SO    \
+                                          : SO * SD + SO)>),               \
+                       dim3(1), dim3(64), 0, stream,                       \
+                       vals.data_ptr<float>(), out.data_ptr<float>());     \
+    found = true;                                                          \
+  }
+  SMALL_SHAPE_LIST(TRY_PROBE)
+#undef TRY_PROBE
+  TORCH_CHECK(found, "train_reduce_probe: no small train kernel has TP=", TP);
+  TORCH_CHECK(hipGetLastError() == hipSuccess, "train_reduce_probe launch");
+  return out;
+}
+
 torch::Tensor eval_tasks_hip(
     torch::Tensor params, torch::Tensor x, torch::Tensor y,
     torch::Tensor task_row, torch::Tensor task_id, torch::Tensor off,
@@ -1239,6 +1426,8 @@ torch::Tensor confusion_tasks_hip(
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("train_fused", &train_fused_hip, "fused batched MLP local training");
+  mod.def("train_reduce_probe", &train_reduce_probe_hip,
+          "test-only: the small train kernel's wave reduce-scatter");
   mod.def("eval_tasks", &eval_tasks_hip, "batched MLP accuracy/loss sweep");
   mod.def("apply_aggregate", &apply_aggregate_hip,
           "masked weighted-average model update");
