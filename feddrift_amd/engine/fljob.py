@@ -166,6 +166,10 @@ class Route(NamedTuple):
 
 
 class FLJob:
+    # A/B switch (profiles/round_ops.json): small fleets' step windows
+    # travel in the train launch's arguments
+    inline_steps = True
+
     def __init__(self, cfg: Config, comm: Communicator,
                  logger: Optional[MetricLogger] = None,
                  dataset: Optional[DriftDataset] = None):
@@ -623,7 +627,7 @@ class FLJob:
                                   self.opt, self.arena.x, self.arena.y,
                                   K, x_mask=plan.x_mask)
         elif route.launch == "staged":
-            off_t, len_t = self._upload_steps(plan, dev)
+            off_t, len_t = self._upload_steps(plan, dev, inline=True)
             rows_t, mo_t, sw_t = self.cached(
                 plan, "train", lambda: self._train_constants(plan))
             # the launch drops its sums when a later pass edits the rows
@@ -663,24 +667,42 @@ class FLJob:
                                           device=self.device)
         return t(rows, np.int64), t(mo, np.int32), t(w, np.float32)
 
-    def _upload_steps(self, plan: TrainPlan, dev: torch.device):
-        """Per-round upload of the [G, E] step windows. On GPU, a pageable
-        torch.as_tensor costs tens of us per array in alloc + staged copy;
-        a per-template pinned double buffer turns both arrays into ONE
-        non-blocking DMA (the buffer slot is event-guarded against reuse
-        while a previous round's copy is still in flight)."""
+    def _upload_steps(self, plan: TrainPlan, dev: torch.device,
+                      inline: bool = False):
+        """The round's [G, E] step windows, as train_fused takes them, out
+        of a per-template staging buffer that is built once and refilled
+        every round (the route is settled when it is built).
+
+        Small fleets on the staged HIP launch (mlp_hip.inline_steps_ok): the
+        buffer is a [2, G, E] CPU tensor. The launch packs its values into
+        the kernel arguments at call time, so nothing is uploaded, no event
+        is waited for, and the buffer is free again when the call returns.
+
+        Otherwise on GPU: a pageable torch.as_tensor costs tens of us per
+        array in alloc + staged copy; a pinned double buffer turns both
+        arrays into ONE non-blocking DMA into the device buffer (the pinned
+        slot is event-guarded against reuse while a previous round's copy
+        is still in flight)."""
         if dev.type != "cuda" or plan.template is None:
             t = lambda a: torch.as_tensor(a, dtype=torch.int64, device=dev)
             return t(plan.step_off), t(plan.step_len)
         G, E = plan.step_off.shape
 
         def build():
+            if inline and self.inline_steps and self._hip_mlp and \
+                    self.backend.inline_steps_ok(self.spec, G, E):
+                buf = torch.empty(2, G, E, dtype=torch.int64)
+                return {"inline": True, "buf": buf, "np": buf.numpy()}
             pin = torch.empty(2, 2, G, E, dtype=torch.int64, pin_memory=True)
             return {
-                "pin": pin, "np": pin.numpy(),
+                "inline": False, "pin": pin, "np": pin.numpy(),
                 "buf": torch.empty(2, G, E, dtype=torch.int64, device=dev),
                 "ev": [torch.cuda.Event(), torch.cuda.Event()], "slot": 0}
         st = self.cached(plan, ("stage", E), build)
+        if st["inline"]:
+            np.copyto(st["np"][0], plan.step_off)
+            np.copyto(st["np"][1], plan.step_len)
+            return st["buf"][0], st["buf"][1]
         slot = st["slot"]
         st["slot"] = slot ^ 1
         st["ev"][slot].synchronize()

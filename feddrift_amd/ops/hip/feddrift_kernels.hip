@@ -554,9 +554,19 @@ struct ScatterReduce {
   }
 };
 
+// Step windows of a small fleet travel in the launch packet: G*E (off, len)
+// pairs as int32, 2 KB of the 4 KB kernel-argument segment. A block's index
+// g*E + e is uniform, so the reads are scalar loads from that segment and
+// the launch needs no upload before it. Larger fleets pass the device arrays
+// (a.step_off != nullptr) and the struct is not read.
+#define INLINE_STEPS 256
+struct StepWin {
+  int2 w[INLINE_STEPS];              // (off, len) of step g*E + e
+};
+
 template <int TD, int TH, int TO, int KIND, int BS>
 __global__ __launch_bounds__(BS)
-void mlp_train_small_kernel(TrainArgs a) {
+void mlp_train_small_kernel(TrainArgs a, StepWin win) {
   constexpr int TP = (KIND == KIND_FNN)
                          ? (TH * TD + TH + TO * TH + TO)
                          : (TO * TD + TO);
@@ -579,11 +589,18 @@ void mlp_train_small_kernel(TrainArgs a) {
   // every load that depends on nothing, or only on rows[g], issues here
   const int64_t row = a.rows[g];
   const int64_t e0 = (int64_t)g * a.E;
+  const bool inl = a.step_off == nullptr;  // windows in the launch packet
   int64_t off_nx = 0;
   int n_nx = 0;
   if (a.E > 0) {
-    off_nx = a.step_off[e0];
-    n_nx = (int)a.step_len[e0];
+    if (inl) {
+      const int2 sw0 = win.w[e0];
+      off_nx = sw0.x;
+      n_nx = sw0.y;
+    } else {
+      off_nx = a.step_off[e0];
+      n_nx = (int)a.step_len[e0];
+    }
   }
   float mk[TD];
 #pragma unroll
@@ -622,8 +639,14 @@ void mlp_train_small_kernel(TrainArgs a) {
     const int64_t off = off_nx;
     const int n = n_nx;
     if (e + 1 < a.E) {  // next step's window, ahead of this step's work
-      off_nx = a.step_off[e0 + e + 1];
-      n_nx = (int)a.step_len[e0 + e + 1];
+      if (inl) {
+        const int2 swn = win.w[e0 + e + 1];
+        off_nx = swn.x;
+        n_nx = swn.y;
+      } else {
+        off_nx = a.step_off[e0 + e + 1];
+        n_nx = (int)a.step_len[e0 + e + 1];
+      }
     }
     if (n == 0) continue;
     const float inv_n = 1.0f / (float)n;
@@ -762,7 +785,53 @@ void train_reduce_probe_kernel(const float* __restrict__ vals,
   X(3, 0, 2, KIND_LR)            \
   X(2, 0, 2, KIND_LR)
 
-static bool launch_small(const TrainArgs& args, int G, hipStream_t stream) {
+static bool small_shape(int D, int H, int O, int kind) {
+#define IS_SHAPE(SD, SH, SO, SK) \
+  if (kind == SK && D == SD && H == SH && O == SO) return true;
+  SMALL_SHAPE_LIST(IS_SHAPE)
+#undef IS_SHAPE
+  return false;
+}
+
+// Whether a launch of G pairs x E steps on this shape may carry its step
+// windows in the launch packet (the values must also fit int32: pack_steps)
+bool inline_steps_ok(int64_t D, int64_t H, int64_t O, int64_t kind,
+                     int64_t G, int64_t E) {
+  return G >= 0 && E >= 0 && G * E <= INLINE_STEPS &&
+         small_shape((int)D, (int)H, (int)O, (int)kind);
+}
+
+// [G, E] CPU int64 windows -> win; false where an off or off + len leaves
+// int32 (the caller then uploads the arrays instead)
+static bool pack_steps(const torch::Tensor& step_off,
+                       const torch::Tensor& step_len, StepWin* win) {
+  const int64_t n = step_off.numel();
+  if (n > INLINE_STEPS) return false;
+  const int64_t* po = step_off.data_ptr<int64_t>();
+  const int64_t* pl = step_len.data_ptr<int64_t>();
+  const int64_t lim = 2147483647LL;
+  for (int64_t i = 0; i < n; ++i) {
+    if (po[i] < 0 || pl[i] < 0 || po[i] > lim || pl[i] > lim ||
+        po[i] + pl[i] > lim)
+      return false;
+    win->w[i] = make_int2((int)po[i], (int)pl[i]);
+  }
+  return true;
+}
+
+// test hook of pack_steps' range rule
+bool steps_fit_inline(torch::Tensor step_off, torch::Tensor step_len) {
+  TORCH_CHECK(!step_off.is_cuda() && !step_len.is_cuda() &&
+              step_off.dtype() == torch::kInt64 &&
+              step_len.dtype() == torch::kInt64 &&
+              step_off.sizes() == step_len.sizes(),
+              "steps_fit_inline: CPU int64 tensors of one shape");
+  StepWin win;
+  return pack_steps(step_off.contiguous(), step_len.contiguous(), &win);
+}
+
+static bool launch_small(const TrainArgs& args, const StepWin& win, int G,
+                         hipStream_t stream) {
   // Block-size choice: every wave of a block redundantly executes the
   // TP x 6-level shuffle reduction, so single-wave (64-thread) blocks cut
   // the total reduction work 4x. Measured same-box across grid sizes
@@ -779,10 +848,10 @@ static bool launch_small(const TrainArgs& args, int G, hipStream_t stream) {
   if (args.kind == SK && args.D == SD && args.H == SH && args.O == SO) {   \
     if (bs64) {                                                            \
       hipLaunchKernelGGL((mlp_train_small_kernel<SD, SH, SO, SK, 64>),     \
-                         dim3(G), dim3(64), 0, stream, args);              \
+                         dim3(G), dim3(64), 0, stream, args, win);         \
     } else {                                                               \
       hipLaunchKernelGGL((mlp_train_small_kernel<SD, SH, SO, SK, THREADS>),\
-                         dim3(G), dim3(THREADS), 0, stream, args);         \
+                         dim3(G), dim3(THREADS), 0, stream, args, win);    \
     }                                                                      \
     return true;                                                           \
   }
@@ -1218,6 +1287,27 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
   const int E = step_off.size(1);
   const bool adam = m.has_value();
 
+  // CPU step windows: into the launch packet where they fit, else this
+  // call uploads them itself (correct, but a blocking pageable copy: the
+  // engine asks inline_steps_ok first and keeps its pinned path otherwise)
+  StepWin win;  // the launch copies it; entries past G*E are never read
+  bool inl = false;
+  if (!step_off.is_cuda()) {
+    TORCH_CHECK(!step_len.is_cuda() && step_off.dtype() == torch::kInt64 &&
+                step_len.dtype() == torch::kInt64 &&
+                step_off.sizes() == step_len.sizes(),
+                "train_fused: CPU step windows must be int64 of one shape");
+    step_off = step_off.contiguous();
+    step_len = step_len.contiguous();
+    inl = inline_steps_ok(D, H, O, kind, G, E) &&
+          step_off.numel() == (int64_t)G * E &&
+          pack_steps(step_off, step_len, &win);
+    if (!inl) {
+      step_off = step_off.to(params.device());
+      step_len = step_len.to(params.device());
+    }
+  }
+
   // chunk size: fit 2P + BC*(D + 2H + O | D + O) in the LDS budget
   const int per_sample = (kind == KIND_FNN) ? (D + 2 * H + O) : (D + O);
   int BC = (LDS_BUDGET_FLOATS - 2 * P) / per_sample;
@@ -1238,8 +1328,8 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
   args.rows = rows.data_ptr<int64_t>();
   args.x = x.data_ptr<float>();
   args.y = y.data_ptr<int64_t>();
-  args.step_off = step_off.data_ptr<int64_t>();
-  args.step_len = step_len.data_ptr<int64_t>();
+  args.step_off = inl ? nullptr : step_off.data_ptr<int64_t>();
+  args.step_len = inl ? nullptr : step_len.data_ptr<int64_t>();
   args.x_mask = x_mask.has_value() ? x_mask->data_ptr<float>() : nullptr;
   args.m = adam ? m->data_ptr<float>() : nullptr;
   args.v = adam ? v->data_ptr<float>() : nullptr;
@@ -1252,7 +1342,8 @@ void train_fused_hip(torch::Tensor params, torch::Tensor rows,
   args.P = P; args.kind = (int)kind; args.opt = adam ? OPT_ADAM : OPT_SGD;
   args.BC = BC;
 
-  if (!launch_small(args, G, c10::hip::getCurrentHIPStream())) {
+  if (!launch_small(args, win, G, c10::hip::getCurrentHIPStream())) {
+    TORCH_CHECK(!inl, "train_fused: inline steps without a small kernel");
     hipLaunchKernelGGL(mlp_train_kernel, dim3(G), dim3(THREADS), lds_bytes,
                        c10::hip::getCurrentHIPStream(), args);
   }
@@ -1429,6 +1520,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("train_reduce_probe", &train_reduce_probe_hip,
           "test-only: the small train kernel's wave reduce-scatter");
   mod.def("eval_tasks", &eval_tasks_hip, "batched MLP accuracy/loss sweep");
+  mod.def("inline_steps_ok", &inline_steps_ok,
+          "may a (d, h, o, kind) launch of G x E steps carry them inline");
+  mod.def("steps_fit_inline", &steps_fit_inline,
+          "test hook: do these CPU step windows pack into int32 pairs");
+  mod.attr("INLINE_STEPS") = INLINE_STEPS;
   mod.def("apply_aggregate", &apply_aggregate_hip,
           "masked weighted-average model update");
   mod.def("ens_vote_multi", &ens_vote_multi_hip,

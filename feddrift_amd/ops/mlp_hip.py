@@ -45,6 +45,19 @@ def _fits_eval(spec: MLPSpec) -> bool:
     return spec.n_params <= EVAL_MAX_P and spec.o <= MAX_O
 
 
+def inline_steps_ok(spec: MLPSpec, G: int, E: int) -> bool:
+    """Whether a train launch of G pairs x E steps on this model carries its
+    step windows in the kernel arguments: train_fused then takes them as
+    CPU int64 tensors and no upload precedes the launch. Past the cap
+    (hip_loader.load().INLINE_STEPS entries), or off the small-kernel shape
+    list, the binding would upload CPU tensors itself with a blocking
+    copy, so callers ask here first and keep their own staging otherwise."""
+    if not _fits_train(spec):
+        return False
+    return bool(hip_loader.load().inline_steps_ok(
+        spec.d, spec.h, spec.o, _KIND[spec.kind], int(G), int(E)))
+
+
 def train_fused(spec: MLPSpec, params_all: torch.Tensor, rows: torch.Tensor,
                 x_arena: torch.Tensor, y_arena: torch.Tensor,
                 step_off: torch.Tensor, step_len: torch.Tensor, opt: Dict,
@@ -55,10 +68,14 @@ def train_fused(spec: MLPSpec, params_all: torch.Tensor, rows: torch.Tensor,
                 partial: Optional[torch.Tensor] = None) -> None:
     """in_params/model_of: stage initial weights straight from the global
     model rows (fuses the round's model broadcast into the launch);
-    sample_w/partial: fused weighted aggregation partial sums."""
+    sample_w/partial: fused weighted aggregation partial sums.
+    step_off/step_len: device tensors, or CPU int64 tensors, which the
+    launch reads at call time (see inline_steps_ok)."""
     if rows.numel() == 0:
         return
     if not _fits_train(spec):
+        dev = params_all.device
+        step_off, step_len = step_off.to(dev), step_len.to(dev)
         anchor = None
         if in_params is not None:
             anchor = in_params[model_of.long()]
